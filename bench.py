@@ -20,9 +20,21 @@ W warmup steps are untimed; exactly K steps are timed between barrier+synchroniz
 the max over ranks is reported. Data is synthetic CIFAR-100-shaped (no network access), weights
 random-init.
 
-Secondary numbers (``"secondary"`` in the JSON line, each measured after the headline with the
-same transport, ``--secondary none`` skips them): the bf16 compute path (N = 1) and the
-co-located topology (N >= 2).
+A plain run does only that: set up, warm up, time the K steps, print the JSON line.
+
+``--full`` adds the secondary numbers (``"secondary"`` in the JSON line, each measured after the
+headline with the same transport; ``--secondary none`` skips them even with ``--full``): the bf16
+compute path, the async PS and the 7-thread async PS (N = 1); the co-located topology and the
+serial (overlap off) round (N >= 2).
+
+``--dump-outputs DIR`` writes what the last timed step computed on rank 0 as ``DIR/<name>.npy``
+(float32): ``loss`` (per-sample losses of the worker's batch), ``grads`` (the worker's gradient
+buffer: the fp16 wire it pushed for the default codec, the dense fp32 gradient the top-k payload is
+encoded from with ``--codec topk``) and ``params`` (the server's parameter state after the update).
+``loss`` and ``grads`` are written only where rank 0 is a worker: with the dedicated topology at
+N >= 2 rank 0 is the server alone and writes ``params`` only. An array above ``DUMP_MAX_ELEMS`` elements is written as a fixed, seeded sample of that many elements
+(the same positions in every run). Model init, data, batch order and augmentation are seeded, so
+two runs with the same arguments start from identical inputs.
 
 Liveness at N >= 2: every rank runs a RoundWatchdog (parallel/liveness.py) over its sync rounds
 (``--round-timeout``, default 120 s): a rank whose round does not complete in time prints what was
@@ -235,6 +247,32 @@ class Run:
             self.chan.drain()
 
 
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MiB of float32, so the three arrays stay well below 64 MB
+DUMP_SEED = 20240607
+
+
+def dump_outputs(run, out_dir):
+    """--dump-outputs: the arrays the last timed step left on this rank, as float32 .npy files."""
+    import numpy as np
+
+    torch.cuda.synchronize()
+    arrays = {}
+    if run.wk is not None:
+        comp = run.wk.compute
+        arrays["loss"] = comp.engine.loss
+        arrays["grads"] = comp.grads
+    if run.server is not None:
+        arrays["params"] = run.server.arena
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        x = x.detach().reshape(-1)
+        if x.numel() > DUMP_MAX_ELEMS:  # fixed sample: the positions depend on the array's length only
+            pos = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(x.numel(), DUMP_MAX_ELEMS,
+                                                                               replace=False))
+            x = x[torch.from_numpy(pos).to(x.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), x.float().cpu().numpy())
+
+
 def rccl_choices(path, limit=24):
     """The distinct algorithm / protocol / channel lines of RCCL's INFO log (NCCL_DEBUG_FILE of this
     rank), printed on stderr and returned for the JSON record; [] when there is no log."""
@@ -324,9 +362,16 @@ def main():
     ap.add_argument("--mode", choices=["sync", "async"], default="sync",
                     help="async: workers push/fetch independently (staleness-weighted server updates)")
     ap.add_argument("--staleness-bound", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the secondary numbers (see --secondary); off by "
+                         "default: a plain run times the headline steps only")
     ap.add_argument("--secondary", choices=["auto", "none"], default="auto",
-                    help="auto: after the headline also time the bf16 compute path (N=1) or the co-located "
-                         "topology (N>=2), reported under 'secondary'")
+                    help="with --full. auto: after the headline also time the bf16 compute path and the async PS "
+                         "(N=1) or the co-located topology and the serial round (N>=2), reported under "
+                         "'secondary'; none: skip them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left on rank 0 (the worker's loss and gradient buffer, "
+                         "the server's params) as DIR/<name>.npy in float32")
     ap.add_argument("--round-timeout", type=float, default=120.0,
                     help="N>=2: a rank whose sync round does not complete within this many seconds reports the "
                          "outstanding collective, aborts its communicator and exits with status 3 (0: off)")
@@ -435,6 +480,8 @@ def main():
                           # time the host spent blocked because it ran len(ring) steps ahead (whole run)
                           "host_wait_ms_total": round(1e3 * wait, 3)}), file=sys.stderr, flush=True)
     run.close()
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(run, a.dump_outputs)
     if rank == 0 and a.mode == "async":
         sm = run.server.final_metrics()
         # average / max_staleness_observed follow the reference (each worker's LAST push,
@@ -448,7 +495,7 @@ def main():
 
     # secondary numbers (same transport): bf16 compute at N=1, the co-located topology at N>=2
     secondary = {}
-    if a.secondary == "auto" and a.mode == "sync" and r18 and topology != "sharded":
+    if a.full and a.secondary == "auto" and a.mode == "sync" and r18 and topology != "sharded":
         # (name, compute dtype, topology, overrides): N = 1 — the bf16 compute path and the async
         # PS (one worker, in-process: the staleness summary of BASELINE's "async staleness"); N >= 2
         # — the co-located topology and the serial (overlap off) round, a same-box A/B of the

@@ -1,10 +1,12 @@
 set -o pipefail
-mkdir -p gpurun_out
-timeout -k 10 120 python -u __graft_entry__.py smoke > gpurun_out/smoke.log 2>&1 || { tail -20 gpurun_out/smoke.log; exit 1; }
-tail -1 gpurun_out/smoke.log
-S0=$SECONDS; timeout -k 10 300 python bench.py > gpurun_out/bench1.json 2>gpurun_out/bench1.err || { tail -20 gpurun_out/bench1.err; exit 1; }
-cat gpurun_out/bench1.json; echo "bench_wall_s $((SECONDS - S0))"
-timeout -k 10 1000 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread -p no:cacheprovider -rf > gpurun_out/gputests.log 2>&1
+# full GPU check: smoke, the benchmark with its secondary numbers, the GPU tests; logs go to $OUT
+OUT=${OUT:-suite_out}
+mkdir -p "$OUT"
+timeout -k 10 120 python -u __graft_entry__.py smoke > "$OUT/smoke.log" 2>&1 || { tail -20 "$OUT/smoke.log"; exit 1; }
+tail -1 "$OUT/smoke.log"
+S0=$SECONDS; timeout -k 10 300 python bench.py --full > "$OUT/bench1.json" 2>"$OUT/bench1.err" || { tail -20 "$OUT/bench1.err"; exit 1; }
+cat "$OUT/bench1.json"; echo "bench_wall_s $((SECONDS - S0))"
+timeout -k 10 1000 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread -p no:cacheprovider -rf > "$OUT/gputests.log" 2>&1
 rc=$?
-tail -15 gpurun_out/gputests.log
+tail -15 "$OUT/gputests.log"
 exit $rc

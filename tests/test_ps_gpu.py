@@ -45,8 +45,9 @@ def test_two_simulated_workers(mode, capsys):
         assert s["global_steps_completed"] == 8
 
 
-def test_bench_contract_single_gpu():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2"],
+def test_bench_contract_single_gpu(tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path / "out")],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     import json
@@ -58,3 +59,34 @@ def test_bench_contract_single_gpu():
         assert k in rec, k
     assert rec["n_gpus"] == 1 and rec["steps"] == 5 and rec["value"] > 0
     assert torch.cuda.is_available()
+    # a plain run measures the headline only; the secondary numbers need --full
+    assert "secondary" not in rec
+    assert rec["ms_per_step"] == pytest.approx(1e3 * 5 * 128 / rec["value"] / 5, rel=1e-3)
+    # --dump-outputs: the last timed step's arrays as float32 .npy, below 64 MB in all
+    import numpy as np
+
+    out = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("loss", "grads", "params")}
+    assert sorted(os.listdir(tmp_path / "out")) == ["grads.npy", "loss.npy", "params.npy"]
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in out.values())
+    assert out["loss"].shape == (128,) and out["loss"].mean() == pytest.approx(rec["last_loss"], abs=1e-3)
+    assert np.abs(out["grads"]).max() > 0 and np.abs(out["params"]).max() > 0
+    assert sum(v.nbytes for v in out.values()) <= 64e6
+
+
+def test_bench_full_secondaries():
+    """bench.py --full: the headline plus every N = 1 secondary number, none of them an error."""
+    import json
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                        "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert rec["steps"] == 5 and rec["value"] > 0 and rec["dtype"] == "fp32"
+    sec = rec["secondary"]
+    assert sorted(sec) == ["async_ps", "async_w7", "bf16_compute"]
+    for name, s in sec.items():
+        assert "error" not in s, (name, s)
+        assert s["value"] > 0, (name, s)
+    assert sec["bf16_compute"]["dtype"] == "bf16" and sec["bf16_compute"]["ms_per_step"] > 0
+    assert sec["async_ps"]["async_staleness"]["rejected_pushes"] == 0
+    assert sec["async_w7"]["workers"] == 7 and len(sec["async_w7"]["async_staleness"]["staleness_histogram"]) > 0
