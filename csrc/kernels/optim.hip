@@ -11,6 +11,7 @@
 //                     forward conv, transposed CRSK for the data-gradient conv); one launch for
 //                     every conv of the model, table-driven.
 #include "common.hpp"
+#include "sgd_tail.hpp"
 
 namespace psx {
 
@@ -25,15 +26,8 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
                                                         float momentum, float wd, int first,
                                                         uint16_t* __restrict__ img) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    float d = ld_grad(g, i) * gscale;
     const float pv = p[i];
-    if (wd != 0.f) d += wd * pv;
-    if (MOM) {
-      const float v = first ? d : momentum * buf[i] + d;
-      buf[i] = v;
-      d = v;
-    }
-    const float nv = pv - lr * d;
+    const float nv = sgd_tail<MOM>(ld_grad(g, i), pv, buf + i, lr, gscale, momentum, wd, first);
     p[i] = nv;
     if (img) img[i] = f2bf(nv);
   }
@@ -97,15 +91,8 @@ __global__ __launch_bounds__(256) void sgd_apply_multi_kernel(float* __restrict_
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     float s = 0.f;
     for (int k = 0; k < srcs.n; ++k) s += ld_grad(reinterpret_cast<const GT*>(srcs.p[k]), i);
-    float d = s * gscale;
     const float pv = p[i];
-    if (wd != 0.f) d += wd * pv;
-    if (MOM) {
-      const float v = first ? d : momentum * buf[i] + d;
-      buf[i] = v;
-      d = v;
-    }
-    const float nv = pv - lr * d;
+    const float nv = sgd_tail<MOM>(s, pv, buf + i, lr, gscale, momentum, wd, first);
     p[i] = nv;
     if (img) img[i] = f2bf(nv);
   }

@@ -98,6 +98,10 @@ _KERNEL_SIGS = {
     "psx_topk_payload_words": (i32, [i32]),
     "psx_topk_encode": (i32, [vp, i32, vp, i64, i32, i32, vp, vp, vp]),
     "psx_topk_decode_add": (i32, [vp, vp, f32, i32, vp]),
+    "psx_q8_payload_bytes": (i64, [i64]),
+    "psx_q8_encode": (i32, [vp, i32, vp, i64, vp, i64, i64, vp]),
+    "psx_q8_apply_multi": (i32, [vp, vp, i32, vp, i64, i64, i64, f32, f32, f32, f32, i32, vp, vp]),
+    "psx_q8_decode": (i32, [vp, vp, i64, i64, i64, f32, i32, vp]),
 }
 
 _RUNTIME_SIGS = {

@@ -548,6 +548,64 @@ def topk_decode_add(payload, dst, scale, kcap):
           "topk_decode_add")
 
 
+def q8_payload_bytes(n: int) -> int:
+    return kernels().psx_q8_payload_bytes(int(n))
+
+
+def _q8_range(n, off, cnt):
+    cnt = n - off if cnt is None else cnt
+    assert off % 256 == 0 and 0 <= off and off + cnt <= n and ((off + cnt) % 256 == 0 or off + cnt == n), \
+        "q8 sub-range: 256-aligned start, end on a block or at n"
+    return int(off), int(cnt)
+
+
+def _q8_payload_ok(payload, n) -> bool:
+    return payload.dtype == torch.uint8 and payload.is_contiguous() and payload.numel() == q8_payload_bytes(n)
+
+
+def q8_encode(g, resid, payload, n=None, off=0, cnt=None):
+    """Error-feedback block-scaled int8 encode of (resid + g)[off:off+cnt] into ``payload`` (the
+    whole arena's q8 payload, parallel/q8.py); resid keeps acc - deq (csrc/kernels/q8.hip).
+    g: fp32 or fp16, >= n elements; resid: fp32, >= n elements."""
+    n = resid.numel() if n is None else n
+    off, cnt = _q8_range(n, off, cnt)
+    assert g.dtype in (torch.float16, torch.float32) and g.numel() >= n and g.device == resid.device, "q8_encode g"
+    assert resid.dtype == torch.float32 and resid.numel() >= n, "q8_encode resid"
+    assert _q8_payload_ok(payload, n) and payload.device == resid.device, "q8_encode payload"
+    check(kernels().psx_q8_encode(ptr(g), int(g.dtype == torch.float16), ptr(resid), n, ptr(payload), off, cnt,
+                                  stream_ptr()), "q8_encode")
+
+
+def q8_apply_multi(p, payloads, lr, gscale=1.0, momentum=0.0, wd=0.0, buf=None, first=False, n=None, img=None, off=0,
+                   cnt=None):
+    """p[off:off+cnt] -= lr*(gscale * sum_k deq(payloads[k]) + wd*p) [momentum]: the server update
+    straight from the gathered q8 payloads, decoded and summed in fp32 in list order (same update
+    tail as sgd_apply_multi). At most 32 payloads; one payload is the async / W = 1 apply."""
+    n = p.numel() if n is None else n
+    off, cnt = _q8_range(n, off, cnt)
+    assert 1 <= len(payloads) <= 32
+    assert p.dtype == torch.float32 and p.numel() >= n, "q8_apply_multi p"
+    assert all(_q8_payload_ok(s, n) and s.device == p.device for s in payloads), "q8_apply_multi"
+    if buf is not None:
+        assert buf.dtype == torch.float32 and buf.numel() >= n and buf.device == p.device, "q8_apply_multi buf"
+    if img is not None:
+        assert img.dtype == torch.bfloat16 and img.numel() >= n and img.device == p.device, "q8_apply_multi img"
+    arr = (C.c_void_p * len(payloads))(*[s.data_ptr() for s in payloads])
+    check(kernels().psx_q8_apply_multi(ptr(p), arr, len(payloads), ptr(buf), n, off, cnt, float(lr), float(gscale),
+                                       float(momentum), float(wd), int(first), ptr(img), stream_ptr()),
+          "q8_apply_multi")
+
+
+def q8_decode(payload, dst, n=None, scale=1.0, add=False, off=0, cnt=None):
+    """dst[off:off+cnt] = [dst +] scale * deq(payload) (fp32 dst of >= n elements)."""
+    n = dst.numel() if n is None else n
+    off, cnt = _q8_range(n, off, cnt)
+    assert dst.dtype == torch.float32 and dst.numel() >= n, "q8_decode dst"
+    assert _q8_payload_ok(payload, n) and payload.device == dst.device, "q8_decode payload"
+    check(kernels().psx_q8_decode(ptr(payload), ptr(dst), n, off, cnt, float(scale), int(add), stream_ptr()),
+          "q8_decode")
+
+
 def grad_aggregate(srcs_dev_ptrs, nsrc, src_fp16, dst, n, scale=1.0, accumulate=False):
     """srcs_dev_ptrs: int64 device tensor holding nsrc device pointers."""
     check(kernels().psx_grad_aggregate(ptr(srcs_dev_ptrs), nsrc, int(src_fp16), ptr(dst),

@@ -54,7 +54,7 @@ def _device_for(local_rank: int):
 
 def _wire_dtype(cfg):
     """Dtype of the worker's dense gradient buffer: fp16 wire (reference cast), fp32 for the
-    uncompressed wire and as the top-k codec's input (the residual is fp32)."""
+    uncompressed wire and as the top-k / q8 codecs' input (their residual is fp32)."""
     return torch.float16 if cfg.codec == "fp16" else torch.float32
 
 
@@ -475,7 +475,7 @@ def make_sync_channel(cfg, t, server, W, layout, device, worker: bool = True, me
     job's survivors otherwise)."""
     codec = FetchCodec(layout, cfg.fetch_codec, device)
     members = list(range(W)) if members is None else list(members)
-    if cfg.overlap and max(1, cfg.sync_steps) == 1 and cfg.codec != "topk":
+    if cfg.overlap and max(1, cfg.sync_steps) == 1 and cfg.dense_wire:
         buckets = plan_buckets(layout, int(cfg.bucket_mb * (1 << 20)) // 2)
         return OverlapSyncChannel(t, server, members=members, codec=codec, buckets=buckets, device=device,
                                   root_worker=server is None or worker)
@@ -672,6 +672,10 @@ def _server_rounds(cfg, server, chan, steps, device, skip, t, ctx):
         from .topk import empty_payload
 
         zeros = empty_payload(server.n, cfg.topk_ratio, device)  # contributes no entries to the gather
+    elif cfg.codec == "q8":
+        from .q8 import empty_payload
+
+        zeros = empty_payload(server.n, device)  # rank 0's slot in the gather; the channel drops it
     else:
         zeros = torch.zeros(server.n, dtype=_wire_dtype(cfg), device=device)
     zbuf = torch.zeros(server.layout.buffer_numel, dtype=torch.float32, device=device) if cfg.bn_sync else None
@@ -687,7 +691,7 @@ def _server_rounds(cfg, server, chan, steps, device, skip, t, ctx):
                     if rb is not None:
                         rb.round_start()
                     chan.fetch(None, None)
-                    if cfg.codec != "topk":
+                    if cfg.dense_wire:
                         zeros.zero_()
                     if zbuf is not None:
                         zbuf.zero_()

@@ -28,7 +28,7 @@ from ..utils import checkpoint as ckpt
 from ..utils import metrics as M
 from ..utils import trace
 from . import control as CP
-from . import topk
+from . import q8, topk
 from .core import APPLY, WAIT, ServerCore
 
 _TRACE = os.environ.get("PSX_TRACE", "0") == "1"
@@ -39,6 +39,13 @@ def arena_sha256(arena: torch.Tensor) -> str:
     import hashlib
 
     return hashlib.sha256(arena.detach().to("cpu", torch.float32).contiguous().numpy().tobytes()).hexdigest()[:32]
+
+
+def _wire_bytes(grads: torch.Tensor, n: int) -> int:
+    """Bytes one push moves: a q8 payload whole, otherwise the first n elements of the buffer."""
+    if grads.dtype == torch.uint8:
+        return grads.numel()
+    return min(n, grads.numel()) * grads.element_size()
 
 
 class ParameterServer:
@@ -72,7 +79,8 @@ class ParameterServer:
 
     # ------------------------------------------------------------------ numerics
     def apply(self, grads: torch.Tensor, weight: float):
-        """p <- p - lr * (weight * g [+ wd p]) [momentum]; grads are fp16 wire or fp32."""
+        """p <- p - lr * (weight * g [+ wd p]) [momentum]; grads are fp16 wire, fp32, or a top-k
+        (int32) / q8 (uint8) payload."""
         trace.mark("psx.apply")
         t0 = self._time_begin()
         if grads.dtype == torch.int32:  # top-k payload (parallel/topk.py)
@@ -82,8 +90,26 @@ class ParameterServer:
                 self._wire_stale = True  # the bf16 image was not written by this update
                 return self.finish_round_apply(self._time_end(t0))
             grads = self._dense_of(grads)
-        self.apply_range(grads[: self.n], weight, 0, self.n)
+        if grads.dtype == torch.uint8:  # q8 payload (parallel/q8.py): decoded inside the update
+            self._apply_q8([grads], weight)
+        else:
+            self.apply_range(grads[: self.n], weight, 0, self.n)
         return self.finish_round_apply(self._time_end(t0))
+
+    def _apply_q8(self, payloads: list, weight: float):
+        """The update from q8 payloads, decoded and summed in fp32 in list order: one fused
+        launch on the device (the weight image, when enabled, written in the same pass); the
+        torch decode into the aggregation buffer on a CPU arena."""
+        if self.device.type == "cuda":
+            from ..ops import kernels as K
+
+            img = self.wire.img[: self.n] if self.wire is not None else None
+            K.q8_apply_multi(self.params, payloads, self.lr, gscale=weight, momentum=self.cfg.momentum,
+                             wd=self.cfg.weight_decay, buf=self.momentum_buf, first=self._mom_first, n=self.n, img=img)
+            return
+        for i, p in enumerate(payloads):
+            self._dense_of(p, add=i > 0)
+        self.apply_range(self.agg, weight, 0, self.n)
 
     # ------------------------------------------------------------------ update timing
     # The reference times the apply itself (server.py:128,140-141) into average_update_time_seconds.
@@ -133,11 +159,13 @@ class ParameterServer:
         return topk.topk_k(self.n, self.cfg.topk_ratio)
 
     def _dense_of(self, payload: torch.Tensor, out: torch.Tensor | None = None, add: bool = False):
-        """Top-k payload -> dense fp32 gradient (into the aggregation buffer by default)."""
+        """Top-k / q8 payload -> dense fp32 gradient (into the aggregation buffer by default)."""
         if out is None:
             if self.agg is None:
                 self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device)
             out = self.agg
+        if payload.dtype == torch.uint8:
+            return q8.decode(payload, self.n, out=out, add=add)
         if not add:
             out.zero_()
         return topk.decode_add(payload, out, 1.0, self._kcap)
@@ -201,7 +229,7 @@ class ParameterServer:
     def _accumulate(self, grads: torch.Tensor, first: bool):
         if self.agg is None:
             self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device)
-        if grads.dtype == torch.int32:
+        if grads.dtype in (torch.int32, torch.uint8):
             self._dense_of(grads, self.agg, add=not first)
             return
         if first:
@@ -256,7 +284,7 @@ class ParameterServer:
         completes, then apply the average. Async: staleness check + weighted apply.
         ``buffers`` (--bn-sync): the worker's BN running statistics, counted only when the core
         takes the push into the round (a duplicate / unknown / rejected push contributes nothing)."""
-        self.bytes_pushed += grads[: self.n].numel() * grads.element_size()
+        self.bytes_pushed += _wire_bytes(grads, self.n)
         res = self.core.on_push(worker_id, local_step)
         self.last_push = res
         if buffers is not None and (res.decision in (WAIT, APPLY) if self.cfg.mode == "sync" else res.accepted):
@@ -267,7 +295,7 @@ class ParameterServer:
                 # entries when the push counter reaches total_workers (server.py:264-288)
                 if res.decision in (WAIT, APPLY):
                     self._pending[worker_id] = (self._dense_of(grads, torch.zeros(self.n, device=self.device))
-                                                if grads.dtype == torch.int32
+                                                if grads.dtype in (torch.int32, torch.uint8)
                                                 else grads[: self.n].to(torch.float32).clone())
                 if res.apply:
                     self._accumulate(sum(self._pending.values()), True)
@@ -282,6 +310,8 @@ class ParameterServer:
                 if grads.dtype == torch.int32:  # decoded into the dense buffer first, as apply_gathered
                     self._dense_of(grads)
                     self.apply(self.agg, res.weight)
+                elif grads.dtype == torch.uint8:  # one-source q8_apply_multi, as apply_q8_sources
+                    self.apply(grads, res.weight)
                 else:
                     trace.mark("psx.apply")
                     t0 = self._time_begin()
@@ -412,6 +442,25 @@ class ParameterServer:
             return True
         return False
 
+    def apply_q8_sources(self, payloads: list, members: list[int], local_steps: list[int],
+                         buffers_sum: torch.Tensor | None = None) -> bool:
+        """Sync round whose W q8 payloads were gathered to rank 0 (one per contributing worker):
+        the bookkeeping of apply_sources, then one launch that decodes and sums them in fp32 in
+        list order inside the update (kernels.q8_apply_multi) — no dense staging buffer."""
+        res = None
+        for wid, ls in zip(members, local_steps):
+            res = self.core.on_push(wid, ls)
+        self.bytes_pushed += sum(p.numel() for p in payloads)
+        if res is None or not res.apply:
+            return False
+        trace.mark("psx.apply")
+        t0 = self._time_begin()
+        self._apply_q8(list(payloads), res.weight)
+        self.finish_round_apply(self._time_end(t0))
+        if buffers_sum is not None:
+            self.set_buffers_from_sum(buffers_sum, len(members))
+        return True
+
     # ------------------------------------------------------------------ checkpoint
     def checkpoint(self, path: str | None = None) -> str:
         step = self.core.global_step
@@ -479,6 +528,8 @@ class ParameterServer:
         if self.cfg.codec == "topk":
             words = topk.payload_words(self._kcap)
             slots = {w: torch.empty(words, dtype=torch.int32, device=self.device) for w in rank_of}
+        elif self.cfg.codec == "q8":
+            slots = {w: torch.empty(q8.payload_bytes(n), dtype=torch.uint8, device=self.device) for w in rank_of}
         else:
             wire_dtype = torch.float16 if self.cfg.codec == "fp16" else torch.float32
             slots = {w: torch.empty(n, dtype=wire_dtype, device=self.device) for w in rank_of}
@@ -552,7 +603,7 @@ class ParameterServer:
                         break
                     if kind == "push":
                         res = self.core.on_push(wid, ls)
-                        self.bytes_pushed += min(n, grads.numel()) * grads.element_size()
+                        self.bytes_pushed += _wire_bytes(grads, n)
                         if res.apply:
                             self.apply(grads, res.weight)
                             if box.get("bufs") is not None:

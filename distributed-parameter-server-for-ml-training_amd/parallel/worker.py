@@ -88,6 +88,8 @@ class InProcessChannel:
 class SyncCollectiveChannel(WatchedRounds):
     """All ranks call push/fetch in lockstep. Rank 0 may or may not train (topology).
 
+    Push (top-k / q8 payloads): gathered to rank 0 and decoded there (ParameterServer.apply_gathered /
+    apply_q8_sources).
     Push (dense wire): the workers' wires are gathered to rank 0 and summed there in fp32 by the
     update kernel, in a fixed worker order — the reference's decode-to-fp32 + average
     (server.py:145-169,232-237), deterministic, and every worker's transfer on its own link.
@@ -173,9 +175,10 @@ class SyncCollectiveChannel(WatchedRounds):
 
     def _push(self, worker_id, grads, local_step, buffers=None):
         sparse = grads.dtype == torch.int32  # top-k payloads cannot be summed by a reduce: gather
+        q8w = grads.dtype == torch.uint8     # nor can q8 payloads (a scale per block and source)
         world = getattr(self.t, "world_size", 1)
-        dense_gather = not sparse and self.agg_mode == "gather" and world > 1
-        if sparse:
+        dense_gather = not sparse and not q8w and self.agg_mode == "gather" and world > 1
+        if sparse or q8w:
             gathered = self.t.gather_to_server(grads)
         elif dense_gather:
             if self.server is not None and self._gbufs is None:
@@ -189,6 +192,9 @@ class SyncCollectiveChannel(WatchedRounds):
             steps = [local_step] * len(self.members)
             if sparse:
                 self.server.apply_gathered(gathered, self.members, steps, buffers_sum=buffers)
+            elif q8w:  # a dedicated server's own slot is the empty payload: dropped here
+                srcs = gathered if self.root_worker else gathered[1:]
+                self.server.apply_q8_sources(srcs, self.members, steps, buffers_sum=buffers)
             elif dense_gather:
                 srcs = ([grads] if self.root_worker else []) + [self._gbufs[r] for r in sorted(self._gbufs)]
                 self.server.apply_sources(srcs, self.members, steps, buffers_sum=buffers)
@@ -291,11 +297,17 @@ class Worker:
         self.images = 0
         self.timer = M.PhaseTimer(device=getattr(compute, "device", None))
         self.sampler = None
-        self.topk = None
+        # the error-feedback encoder of the push codec (owns the residual and the payload buffer):
+        # top-k (parallel/topk.py) or block-scaled int8 (parallel/q8.py); None = dense wire
+        self.encoder = None
         if cfg.codec == "topk":
             from .topk import TopKCodec
 
-            self.topk = TopKCodec(compute.layout.param_numel, cfg.topk_ratio, getattr(compute, "device", "cpu"))
+            self.encoder = TopKCodec(compute.layout.param_numel, cfg.topk_ratio, getattr(compute, "device", "cpu"))
+        elif cfg.codec == "q8":
+            from .q8 import Q8Codec
+
+            self.encoder = Q8Codec(compute.layout.param_numel, getattr(compute, "device", "cpu"))
 
     # ---------------------------------------------------------------- reference API
     def connect_to_server(self):
@@ -349,10 +361,10 @@ class Worker:
         if self.cfg.bn_sync:
             bufs = self.compute.local_arena[self.compute.layout.param_numel:]
         g = self.compute.grads
-        if self.topk is not None:  # --codec topk: error-feedback top-k payload (parallel/topk.py)
-            if self.recover is not None:
+        if self.encoder is not None:  # --codec topk / q8: error-feedback payload
+            if self.recover is not None and self.cfg.codec == "topk":  # sync shrink runs dense or top-k only
                 self._snapshot_resid()
-            g = self.topk.encode(g)
+            g = self.encoder.encode(g)
         ok = self.channel.push(self.worker_id, g, self.global_step_cache, buffers=bufs)
         self._pushes += 1
         if not ok:
@@ -360,7 +372,7 @@ class Worker:
         return ok
 
     def _snapshot_resid(self):
-        r = self.topk.resid
+        r = self.encoder.resid
         if self._rsnap is None:
             d = self._rsnap_depth()
             self._rsnap = ([torch.empty_like(r) for _ in range(d)], [-1] * d)
@@ -371,13 +383,13 @@ class Worker:
 
     def _rewind_resid(self, rounds_kept: int):
         """The top-k residual back to its state before round ``rounds_kept``'s encode."""
-        if self.topk is None or self._rsnap is None:
+        if self.encoder is None or self._rsnap is None:
             self._pushes = rounds_kept
             return
         bufs, rounds = self._rsnap
         k = rounds_kept % len(bufs)
         if rounds[k] == rounds_kept:
-            self.topk.resid.copy_(bufs[k])
+            self.encoder.resid.copy_(bufs[k])
         elif rounds_kept != self._pushes:
             raise RuntimeError(f"top-k residual of round {rounds_kept} is not in the snapshot ring "
                                f"(pushed {self._pushes}, ring {rounds})")

@@ -50,7 +50,7 @@ class PSConfig:
     gpus: int = 1                  # processes / GPUs on this node (1 = server+worker co-located)
     topology: str = "colocated"    # colocated: rank 0 = PS + worker 0; dedicated: rank 0 = PS only;
     #                                sharded: every rank = worker + 1/world of the PS (parallel/sharded.py)
-    codec: str = "fp16"            # none (fp32 wire) | fp16 (reference) | topk
+    codec: str = "fp16"            # none (fp32 wire) | fp16 (reference) | q8 (block-scaled int8) | topk
     topk_ratio: float = 0.01
     # compute dtype of the HIP engine: fp32 = the reference's training precision (worker.py:333-348;
     # exact-f32 MFMA), bf16 = the fast path (bf16 operands, fp32 accumulation and master weights)
@@ -111,8 +111,8 @@ class PSConfig:
             raise ValueError("Number of workers must be between 1 and 32")
         if self.eval_workers not in ("all", "first"):
             raise ValueError("--eval-workers must be all or first")
-        if self.codec not in ("none", "fp16", "topk"):
-            raise ValueError(f"--codec must be none, fp16 or topk, got {self.codec!r}")
+        if self.codec not in ("none", "fp16", "q8", "topk"):
+            raise ValueError(f"--codec must be none, fp16, q8 or topk, got {self.codec!r}")
         if self.topology not in ("colocated", "dedicated", "sharded"):
             raise ValueError(f"--topology must be colocated, dedicated or sharded, got {self.topology!r}")
         if self.topology == "sharded":  # parallel/sharded.py scope
@@ -151,11 +151,17 @@ class PSConfig:
 
     def resolve_overlap(self, world: int) -> bool:
         """--overlap / --no-overlap, or auto: bucketed rounds when there are peers to exchange
-        with and the round qualifies (sync, one push per batch, dense wire, rank-0 server)."""
+        with and the round qualifies (sync, one push per batch, dense wire, rank-0 server). The
+        error-feedback codecs (q8, topk) encode the whole gradient at once: no bucketed rounds."""
         if self.overlap is None:
             self.overlap = (world > 1 and self.mode == "sync" and max(1, self.sync_steps) == 1
-                            and self.codec != "topk" and self.topology != "sharded")
+                            and self.dense_wire and self.topology != "sharded")
         return bool(self.overlap)
+
+    @property
+    def dense_wire(self) -> bool:
+        """The push is the dense gradient buffer itself (fp16 cast or fp32), not an encoded payload."""
+        return self.codec in ("fp16", "none")
 
     def to_json(self) -> str:
         return json.dumps(dataclasses.asdict(self), sort_keys=True)
@@ -181,7 +187,7 @@ def add_arguments(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
     A("--num-classes", type=int, default=None)
     A("--gpus", "--nproc", dest="gpus", type=int, default=None)
     A("--topology", choices=["colocated", "dedicated", "sharded"], default=None)
-    A("--codec", choices=["none", "fp16", "topk"], default=None)
+    A("--codec", choices=["none", "fp16", "q8", "topk"], default=None)
     A("--topk-ratio", type=float, default=None)
     A("--dtype", choices=["fp32", "bf16"], default=None,
       help="worker compute precision: fp32 (reference, default) or bf16 (fast path)")

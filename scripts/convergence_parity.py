@@ -10,6 +10,9 @@
 * ``psx_fp32``        the psx parameter server, W = 1 sync loopback (Worker -> InProcessChannel ->
                       ParameterServer), fp32 HIP engine, fp16 gradient wire (the reference codec).
 * ``psx_fp32_wire32`` the same with the fp32 wire (--codec none).
+* ``psx_fp32_q8``     the same with the block-scaled int8 wire and error feedback (--codec q8); also
+                      compared against ``psx_fp32`` (``q8_vs_psx_fp32`` in the JSON), next to the
+                      torch seed-to-seed spread.
 * ``psx_bf16``        the bf16 HIP engine (fast path), fp16 wire, bf16conv fetch.
 * ``psx_fp32_reference_bn`` psx_fp32 with the reference's BN semantics (no --bn-sync): same
                       training curve, but the evaluation runs on never-learned running statistics.
@@ -199,6 +202,7 @@ def main():
                      ("torch_fp32_init1", lambda: run_torch(args, train, test, 1)),
                      ("psx_fp32", lambda: run_psx(args, train, test, "fp32", "fp16")),
                      ("psx_fp32_wire32", lambda: run_psx(args, train, test, "fp32", "none")),
+                     ("psx_fp32_q8", lambda: run_psx(args, train, test, "fp32", "q8")),
                      ("psx_bf16", lambda: run_psx(args, train, test, "bf16", "fp16")),
                      ("psx_fp32_reference_bn", lambda: run_psx(args, train, test, "fp32", "fp16", bn_sync=False))):
         runs[name] = fn()
@@ -216,6 +220,11 @@ def main():
                      "last100_loss_diff": float(np.mean(r["loss"][-100:]) - np.mean(runs["torch_fp32"]["loss"][-100:])),
                      "test_acc_diff_pp": r["test_acc"] - runs["torch_fp32"]["test_acc"]}
         print(f"  vs torch_fp32: {name:18s} {json.dumps(cmp[name])}", flush=True)
+    d = smooth(runs["psx_fp32_q8"]["loss"], args.window) - smooth(runs["psx_fp32"]["loss"], args.window)
+    q8cmp = {"max_abs_smoothed_loss_diff": float(np.max(np.abs(d))),
+             "mean_abs_smoothed_loss_diff": float(np.mean(np.abs(d))),
+             "torch_seed_spread_mean_abs": cmp["torch_fp32_init1"]["mean_abs_smoothed_loss_diff"]}
+    print(f"  psx_fp32_q8 vs psx_fp32: {json.dumps(q8cmp)}", flush=True)
     w4 = {}
     if not args.skip_w4:
         for bn in (False, True):
@@ -224,7 +233,7 @@ def main():
             print(f"W=4 {key}: {json.dumps(w4[key])}", flush=True)
     out = {"config": vars(args), "data": "synthetic_hard: 4x4 class prototypes (std 12) + pixel noise (std 64), "
                                           "20% label noise, 100 classes",
-           "runs": runs, "vs_torch_fp32": cmp, "w4_sync": w4}
+           "runs": runs, "vs_torch_fp32": cmp, "q8_vs_psx_fp32": q8cmp, "w4_sync": w4}
     with open(os.path.join(args.out, "convergence_parity.json"), "w") as f:
         json.dump(out, f)
     try:
