@@ -1,0 +1,343 @@
+// Layer-wise adaptive server update (LARS: You, Gitman, Ginsburg 2017), --optimizer lars.
+//
+// The SGD kernels (optim.hip, q8.hip) see the trainable prefix of the arena as one anonymous run
+// of floats. LARS scales every tensor's update by a trust ratio of two norms, so this file carries
+// the tensor boundaries of models/layout.py to the device (LarsSeg, one record per trainable
+// tensor) and reduces per tensor, in two launches over one flat grid of
+// (tensor, chunk of kLarsChunk elements) workgroups:
+//
+//   lars_norms : s = sum_k decode(g_k) in fp32 in source order k = 0..W-1 (exactly the sum of
+//                sgd_apply_multi), written as fp32 to the staging buffer; one {sum s^2, sum w^2}
+//                partial per workgroup. The dense entry takes s already in the staging buffer
+//                (q8 / top-k payloads decoded by their own kernels) and only reduces.
+//   lars_apply : every workgroup re-derives its tensor's ratio from the tensor's partials,
+//                  lambda = trust * |w| / (gscale * |s| + wd * |w| + eps)   (1 if |w| or |s| is 0,
+//                  and for 1-D tensors, which also take no weight decay),
+//                and applies the shared update tail (sgd_tail.hpp) with gscale and wd scaled by
+//                lambda: d = lambda * (gscale * s + wd * w); momentum; p -= lr * v; bf16 image.
+//
+// Determinism (the project's default mode): no atomics. A lane accumulates its elements serially
+// with explicit fma in a fixed element order, partials are double from the cross-lane step on
+// (xor shuffle tree over the wave, the four waves summed in order through LDS), and the
+// partials of a tensor are summed with a fixed lane assignment and the same trees. Which element
+// a lane owns depends only on the chunk's position in the arena, never on pointer alignment, so
+// the multi-source and the dense entry end in the same bits for the same s.
+//
+// Tensor offsets are arbitrary (a 100-element bias, a 1728-element stem), so a chunk starts at any
+// element: its head up to the next multiple of 8 arena elements and its tail are scalar accesses,
+// the body is 8 elements per lane (one 16-byte fp16 load per source, two 16-byte fp32 accesses) when
+// every base pointer is 16-byte aligned, and the same 8 elements with scalar accesses otherwise.
+#include "common.hpp"
+#include "sgd_tail.hpp"
+
+namespace psx {
+
+constexpr int kLarsChunk = 8192;  // elements per workgroup: 32 body elements per lane
+constexpr int kLarsMaxSrc = 32;   // reference server.py:424-426 caps the job at 32 workers
+
+struct LarsSeg {
+  long offset;      // first arena element of the tensor
+  long numel;
+  int adapt;        // 1: trust ratio + weight decay (ndim > 1); 0: lambda = 1, no weight decay
+  int first_block;  // first workgroup of the tensor in the flat grid
+};
+
+struct LarsSrcs {
+  const void* p[kLarsMaxSrc];
+  int n;
+};
+
+// which tensor owns this workgroup: every record's block range tested in parallel (-1: none)
+PSX_DEV int lars_find(const LarsSeg* __restrict__ table, int ntensors, int nblocks, int* sh) {
+  if (threadIdx.x == 0) *sh = -1;
+  __syncthreads();
+  const int bid = blockIdx.x;
+  for (int k = threadIdx.x; k < ntensors; k += blockDim.x) {
+    const int lo = table[k].first_block;
+    const int hi = k + 1 < ntensors ? table[k + 1].first_block : nblocks;
+    if (lo <= bid && bid < hi) *sh = k;
+  }
+  __syncthreads();
+  return *sh;
+}
+
+// arena range [a0, a1) of one chunk: scalar head [a0, ha), 8-element groups [ha, tb), tail [tb, a1)
+struct LarsRange {
+  long a0, ha, tb, a1;
+};
+PSX_DEV LarsRange lars_range(const LarsSeg& s, int chunk, long n) {
+  LarsRange r;
+  const long end = min(s.offset + s.numel, n);
+  r.a0 = min(s.offset + (long)chunk * kLarsChunk, end);
+  r.a1 = min(r.a0 + kLarsChunk, end);
+  r.ha = min(r.a1, (r.a0 + 7) & ~7L);
+  r.tb = r.ha + ((r.a1 - r.ha) & ~7L);
+  return r;
+}
+
+PSX_DEV float lars_ld(const uint16_t* g, long i) { return (float)__builtin_bit_cast(_Float16, g[i]); }
+PSX_DEV float lars_ld(const float* g, long i) { return g[i]; }
+
+PSX_DEV double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// block-wide {a, b} in double: wave trees, then the four waves in order (every thread gets both)
+PSX_DEV void lars_block_sum2(double& a, double& b, double (*red)[4]) {
+  a = wave_sum_f64(a);
+  b = wave_sum_f64(b);
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  if (l == 0) {
+    red[0][w] = a;
+    red[1][w] = b;
+  }
+  __syncthreads();
+  a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+  b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+}
+
+// GT: wire element (fp16 bits or fp32). DENSE: s is already in `stage` (no sources, no rewrite).
+// VEC: 16-byte accesses in the body (every base pointer 16-byte aligned).
+template <typename GT, bool DENSE, bool VEC>
+__global__ __launch_bounds__(256) void lars_norms_kernel(const float* __restrict__ p, LarsSrcs srcs,
+                                                         float* __restrict__ stage, long n,
+                                                         const LarsSeg* __restrict__ table, int ntensors, int nblocks,
+                                                         double* __restrict__ partials) {
+  __shared__ int sh_t;
+  __shared__ double red[2][4];
+  const int t = lars_find(table, ntensors, nblocks, &sh_t);
+  if (t < 0) return;  // block-uniform
+  const LarsSeg seg = table[t];
+  const LarsRange r = lars_range(seg, blockIdx.x - seg.first_block, n);
+  const int tid = threadIdx.x;
+  float ss = 0.f, ww = 0.f;
+  auto one = [&](long i) {
+    float s;
+    if constexpr (DENSE) {
+      s = stage[i];
+    } else {
+      s = 0.f;
+      for (int k = 0; k < srcs.n; ++k) s += lars_ld(reinterpret_cast<const GT*>(srcs.p[k]), i);
+      stage[i] = s;
+    }
+    const float w = p[i];
+    ss = __builtin_fmaf(s, s, ss);
+    ww = __builtin_fmaf(w, w, ww);
+  };
+  if (tid < r.ha - r.a0) one(r.a0 + tid);
+  const long ng = (r.tb - r.ha) >> 3;
+  for (long q = tid; q < ng; q += 256) {
+    const long i = r.ha + 8 * q;
+    if constexpr (VEC) {
+      float s[8];
+      if constexpr (DENSE) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(stage + i);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(stage + i + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          s[j] = a[j];
+          s[4 + j] = b[j];
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s[j] = 0.f;
+        for (int k = 0; k < srcs.n; ++k) {
+          if constexpr (sizeof(GT) == 2) {
+            const u32x4 gv = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint16_t*>(srcs.p[k]) + i);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              s[2 * j] += (float)__builtin_bit_cast(_Float16, (uint16_t)(gv[j] & 0xffff));
+              s[2 * j + 1] += (float)__builtin_bit_cast(_Float16, (uint16_t)(gv[j] >> 16));
+            }
+          } else {
+            const float* g = reinterpret_cast<const float*>(srcs.p[k]) + i;
+            const f32x4 a = *reinterpret_cast<const f32x4*>(g);
+            const f32x4 b = *reinterpret_cast<const f32x4*>(g + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              s[j] += a[j];
+              s[4 + j] += b[j];
+            }
+          }
+        }
+        *reinterpret_cast<f32x4*>(stage + i) = (f32x4){s[0], s[1], s[2], s[3]};
+        *reinterpret_cast<f32x4*>(stage + i + 4) = (f32x4){s[4], s[5], s[6], s[7]};
+      }
+      const f32x4 w0 = *reinterpret_cast<const f32x4*>(p + i);
+      const f32x4 w1 = *reinterpret_cast<const f32x4*>(p + i + 4);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {  // the scalar form's order: element by element
+        const float w = j < 4 ? w0[j] : w1[j - 4];
+        ss = __builtin_fmaf(s[j], s[j], ss);
+        ww = __builtin_fmaf(w, w, ww);
+      }
+    } else {
+      for (int j = 0; j < 8; ++j) one(i + j);
+    }
+  }
+  if (tid < r.a1 - r.tb) one(r.tb + tid);
+  double dss = (double)ss, dww = (double)ww;
+  lars_block_sum2(dss, dww, red);
+  if (tid == 0) {
+    partials[2 * (long)blockIdx.x] = dss;
+    partials[2 * (long)blockIdx.x + 1] = dww;
+  }
+}
+
+template <bool MOM, bool VEC>
+__global__ __launch_bounds__(256) void lars_apply_kernel(float* __restrict__ p, const float* __restrict__ stage,
+                                                         float* __restrict__ buf, long n,
+                                                         const LarsSeg* __restrict__ table, int ntensors, int nblocks,
+                                                         const double* __restrict__ partials,
+                                                         float* __restrict__ ratios, float lr, float gscale,
+                                                         float momentum, float wd, float trust, float eps, int first,
+                                                         uint16_t* __restrict__ img) {
+  __shared__ int sh_t;
+  __shared__ double red[2][4];
+  const int t = lars_find(table, ntensors, nblocks, &sh_t);
+  if (t < 0) return;  // block-uniform
+  const LarsSeg seg = table[t];
+  const int chunk = blockIdx.x - seg.first_block;
+  const LarsRange r = lars_range(seg, chunk, n);
+  const int tid = threadIdx.x;
+  float lam = 1.f, gs = gscale, wdl = 0.f;
+  if (seg.adapt) {  // block-uniform
+    // the tensor's partials: partial j on lane (j - first) % 256, lane-serial, then the fixed trees
+    const long b0 = seg.first_block, b1 = b0 + (seg.numel + kLarsChunk - 1) / kLarsChunk;
+    double ss = 0.0, ww = 0.0;
+    for (long j = b0 + tid; j < b1; j += 256) {
+      ss += partials[2 * j];
+      ww += partials[2 * j + 1];
+    }
+    lars_block_sum2(ss, ww, red);
+    const double gn = (double)gscale * sqrt(ss), wn = sqrt(ww);
+    if (wn > 0.0 && gn > 0.0) lam = (float)((double)trust * wn / (gn + (double)wd * wn + (double)eps));
+    gs = lam * gscale;
+    wdl = lam * wd;
+  }
+  if (chunk == 0 && tid == 0) ratios[t] = lam;
+  auto one = [&](long i) {
+    const float pv = p[i];
+    const float nv = sgd_tail<MOM>(stage[i], pv, buf + i, lr, gs, momentum, wdl, first);
+    p[i] = nv;
+    if (img) img[i] = f2bf(nv);
+  };
+  if (tid < r.ha - r.a0) one(r.a0 + tid);
+  const long ng = (r.tb - r.ha) >> 3;
+  for (long q = tid; q < ng; q += 256) {
+    const long i = r.ha + 8 * q;
+    if constexpr (VEC) {
+      float s[8], pv[8], bv[8];
+      ld8(stage + i, s);
+      ld8(p + i, pv);
+      if (MOM && !first) ld8(buf + i, bv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pv[j] = sgd_tail<MOM>(s[j], pv[j], &bv[j], lr, gs, momentum, wdl, first);
+      st8(p + i, pv);
+      if (MOM) st8(buf + i, bv);
+      if (img) {
+        const u32x4 o = {pack_bf2(pv[0], pv[1]), pack_bf2(pv[2], pv[3]), pack_bf2(pv[4], pv[5]),
+                         pack_bf2(pv[6], pv[7])};
+        *reinterpret_cast<u32x4*>(img + i) = o;
+      }
+    } else {
+      for (int j = 0; j < 8; ++j) one(i + j);
+    }
+  }
+  if (tid < r.a1 - r.tb) one(r.tb + tid);
+}
+
+}  // namespace psx
+
+using namespace psx;
+
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+static int lars_launch_apply(float* p, float* stage, float* buf, long n, const void* table, int ntensors, int nblocks,
+                             double* partials, float* ratios, float lr, float gscale, float momentum, float wd,
+                             float trust, float eps, int first, void* img, hipStream_t st) {
+  const bool mom = buf != nullptr && momentum != 0.f;
+  const bool vec = al16(p) && al16(stage) && (!mom || al16(buf)) && al16(img);
+  const LarsSeg* tb = (const LarsSeg*)table;
+  uint16_t* im = (uint16_t*)img;
+#define PSX_LA(M, V)                                                                                             \
+  hipLaunchKernelGGL((lars_apply_kernel<M, V>), dim3(nblocks), dim3(256), 0, st, p, (const float*)stage, buf, n, \
+                     tb, ntensors, nblocks, (const double*)partials, ratios, lr, gscale, momentum, wd, trust,    \
+                     eps, first, im)
+  if (mom && vec) PSX_LA(true, true);
+  else if (mom) PSX_LA(true, false);
+  else if (vec) PSX_LA(false, true);
+  else PSX_LA(false, false);
+#undef PSX_LA
+  return (int)hipGetLastError();
+}
+
+static bool lars_args_ok(const void* p, const void* stage, long n, const void* table, int ntensors, int nblocks,
+                         const void* partials, const void* ratios) {
+  return p && stage && table && partials && ratios && n > 0 && ntensors > 0 && nblocks > 0;
+}
+
+extern "C" {
+
+int psx_lars_table_size() { return (int)sizeof(LarsSeg); }
+int psx_lars_chunk() { return kLarsChunk; }
+
+// The LARS update from nsrc gathered gradient wires (host array of nsrc <= 32 device pointers, all
+// fp16 or all fp32, >= n elements each): two launches on `st`, no host synchronisation.
+//   stage    : fp32 [n], receives the fp32 sum of the sources (must not alias a source)
+//   table    : device array of ntensors LarsSeg covering [0, n), first_block ascending;
+//              nblocks = sum of ceil(numel / psx_lars_chunk())
+//   partials : double [2 * nblocks] scratch;  ratios: float [ntensors], lambda of every tensor
+//   buf / first / img: as psx_sgd_apply_multi
+int psx_lars_apply_multi(float* p, const void* const* srcs, int nsrc, int grad_fp16, float* stage, float* buf, long n,
+                         const void* table, int ntensors, int nblocks, double* partials, float* ratios, float lr,
+                         float gscale, float momentum, float wd, float trust, float eps, int first, void* img,
+                         hipStream_t st) {
+  if (nsrc < 1 || nsrc > kLarsMaxSrc || !srcs) return (int)hipErrorInvalidValue;
+  if (!lars_args_ok(p, stage, n, table, ntensors, nblocks, partials, ratios)) return (int)hipErrorInvalidValue;
+  LarsSrcs sl{};
+  sl.n = nsrc;
+  bool vec = al16(p) && al16(stage);
+  for (int k = 0; k < nsrc; ++k) {
+    if (!srcs[k] || srcs[k] == (const void*)stage) return (int)hipErrorInvalidValue;
+    sl.p[k] = srcs[k];
+    vec = vec && al16(srcs[k]);
+  }
+  const LarsSeg* tb = (const LarsSeg*)table;
+#define PSX_LN(G, V)                                                                                              \
+  hipLaunchKernelGGL((lars_norms_kernel<G, false, V>), dim3(nblocks), dim3(256), 0, st, (const float*)p, sl, stage, \
+                     n, tb, ntensors, nblocks, partials)
+  if (grad_fp16 && vec) PSX_LN(uint16_t, true);
+  else if (grad_fp16) PSX_LN(uint16_t, false);
+  else if (vec) PSX_LN(float, true);
+  else PSX_LN(float, false);
+#undef PSX_LN
+  const int rc = (int)hipGetLastError();
+  if (rc) return rc;
+  return lars_launch_apply(p, stage, buf, n, table, ntensors, nblocks, partials, ratios, lr, gscale, momentum, wd,
+                           trust, eps, first, img, st);
+}
+
+// The dense entry: `stage` already holds the fp32 gradient sum (q8 / top-k payloads decoded into
+// it, or an accumulated round); norms only, no rewrite, then the same apply.
+int psx_lars_apply(float* p, float* stage, float* buf, long n, const void* table, int ntensors, int nblocks,
+                   double* partials, float* ratios, float lr, float gscale, float momentum, float wd, float trust,
+                   float eps, int first, void* img, hipStream_t st) {
+  if (!lars_args_ok(p, stage, n, table, ntensors, nblocks, partials, ratios)) return (int)hipErrorInvalidValue;
+  const LarsSrcs sl{};
+  const LarsSeg* tb = (const LarsSeg*)table;
+  if (al16(p) && al16(stage))
+    hipLaunchKernelGGL((lars_norms_kernel<float, true, true>), dim3(nblocks), dim3(256), 0, st, (const float*)p, sl,
+                       stage, n, tb, ntensors, nblocks, partials);
+  else
+    hipLaunchKernelGGL((lars_norms_kernel<float, true, false>), dim3(nblocks), dim3(256), 0, st, (const float*)p, sl,
+                       stage, n, tb, ntensors, nblocks, partials);
+  const int rc = (int)hipGetLastError();
+  if (rc) return rc;
+  return lars_launch_apply(p, stage, buf, n, table, ntensors, nblocks, partials, ratios, lr, gscale, momentum, wd,
+                           trust, eps, first, img, st);
+}
+
+}  // extern "C"

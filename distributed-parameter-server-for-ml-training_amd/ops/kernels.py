@@ -606,6 +606,99 @@ def q8_decode(payload, dst, n=None, scale=1.0, add=False, off=0, cnt=None):
           "q8_decode")
 
 
+LARS_CHUNK = 8192  # kLarsChunk in csrc/kernels/lars.hip: elements per workgroup of the LARS grid
+_LARS_SEG = [("offset", "<i8"), ("numel", "<i8"), ("adapt", "<i4"), ("first_block", "<i4")]  # LarsSeg
+
+
+class LarsTable:
+    """The per-tensor segment table of the LARS update on the device (csrc/kernels/lars.hip
+    LarsSeg: one record per trainable tensor, in arena order) with the scratch the two launches
+    need: one {sum s^2, sum w^2} double pair per workgroup, and the float [ntensors] trust-ratio
+    table the apply fills (``ratios``; 1 for the tensors that are not adapted)."""
+
+    def __init__(self, layout, device):
+        import numpy as np
+
+        ents = sorted((e for e in layout.entries.values() if e.region == "param" and e.numel > 0),
+                      key=lambda e: e.offset)
+        assert ents, "lars_table: no trainable tensors"
+        rec = np.zeros(len(ents), dtype=_LARS_SEG)
+        blk, end = 0, 0
+        for i, e in enumerate(ents):
+            assert e.offset >= end, f"lars_table: {e.name} overlaps its predecessor"
+            rec[i] = (e.offset, e.numel, int(len(e.shape) > 1), blk)
+            blk += -(-e.numel // LARS_CHUNK)
+            end = e.offset + e.numel
+        assert end <= layout.param_numel and blk < 2 ** 31, "lars_table"
+        self.device = torch.device(device)
+        self.n = int(layout.param_numel)
+        self.ntensors, self.nblocks = len(ents), int(blk)
+        self.names = [e.name for e in ents]
+        self.adapt = [bool(a) for a in rec["adapt"]]
+        if self.device.type == "cuda":
+            assert kernels().psx_lars_table_size() == rec.dtype.itemsize, "LarsSeg layout"
+            assert kernels().psx_lars_chunk() == LARS_CHUNK, "kLarsChunk"
+        self.dev = torch.from_numpy(rec.view(np.uint8).copy()).to(self.device)
+        self.device = self.dev.device  # with the device index filled in
+        self.partials = torch.zeros(2 * self.nblocks, dtype=torch.float64, device=self.device)
+        self.ratios = torch.ones(self.ntensors, dtype=torch.float32, device=self.device)
+
+    def records(self):
+        """The device table read back: a numpy record array (offset, numel, adapt, first_block)."""
+        import numpy as np
+
+        return self.dev.cpu().numpy().view(np.dtype(_LARS_SEG))
+
+
+def lars_table(layout, device) -> LarsTable:
+    return LarsTable(layout, device)
+
+
+def _lars_common(p, stage, table, buf, img, n, what):
+    n = table.n if n is None else n
+    assert n == table.n and p.dtype == torch.float32 and p.is_contiguous() and p.numel() >= n, f"{what} p"
+    assert p.device == table.device and p.device.type == "cuda", f"{what} device"
+    assert stage.dtype == torch.float32 and stage.is_contiguous() and stage.numel() >= n and stage.device == p.device, \
+        f"{what} stage"
+    if buf is not None:
+        assert buf.dtype == torch.float32 and buf.numel() >= n and buf.device == p.device, f"{what} buf"
+    if img is not None:
+        assert img.dtype == torch.bfloat16 and img.numel() >= n and img.device == p.device, f"{what} img"
+    return n
+
+
+def lars_apply_multi(p, srcs, stage, table: LarsTable, lr, gscale=1.0, momentum=0.0, wd=0.0, trust=0.001, eps=1e-8,
+                     buf=None, first=False, n=None, img=None):
+    """The LARS server update from the W gathered wires (csrc/kernels/lars.hip): ``stage``
+    receives s = sum_k srcs[k] (fp32, list order, as sgd_apply_multi forms it); every tensor of
+    ``table`` with ndim > 1 is updated with d = lambda * (gscale * s + wd * p), lambda = trust *
+    |p| / (gscale * |s| + wd * |p| + eps) (1 when a norm is 0), the 1-D ones with d = gscale * s;
+    then v = first ? d : momentum * v + d, p -= lr * v. All sources fp16 or all fp32; at most 32.
+    Two launches on the current stream, no host synchronisation."""
+    n = _lars_common(p, stage, table, buf, img, n, "lars_apply_multi")
+    assert 1 <= len(srcs) <= 32
+    fp16 = srcs[0].dtype == torch.float16
+    assert srcs[0].dtype in (torch.float16, torch.float32), "lars_apply_multi"
+    assert all(s.dtype == srcs[0].dtype and s.numel() >= n and s.device == p.device and s.is_contiguous()
+               and s.data_ptr() != stage.data_ptr() for s in srcs), "lars_apply_multi"
+    arr = (C.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
+    check(kernels().psx_lars_apply_multi(ptr(p), arr, len(srcs), int(fp16), ptr(stage), ptr(buf), n, ptr(table.dev),
+                                         table.ntensors, table.nblocks, ptr(table.partials), ptr(table.ratios),
+                                         float(lr), float(gscale), float(momentum), float(wd), float(trust),
+                                         float(eps), int(first), ptr(img), stream_ptr()), "lars_apply_multi")
+
+
+def lars_apply(p, stage, table: LarsTable, lr, gscale=1.0, momentum=0.0, wd=0.0, trust=0.001, eps=1e-8, buf=None,
+               first=False, n=None, img=None):
+    """lars_apply_multi for a gradient sum that is already dense fp32 in ``stage`` (decoded q8 /
+    top-k payloads, an accumulated round): norms only, no rewrite, then the same apply."""
+    n = _lars_common(p, stage, table, buf, img, n, "lars_apply")
+    check(kernels().psx_lars_apply(ptr(p), ptr(stage), ptr(buf), n, ptr(table.dev), table.ntensors, table.nblocks,
+                                   ptr(table.partials), ptr(table.ratios), float(lr), float(gscale), float(momentum),
+                                   float(wd), float(trust), float(eps), int(first), ptr(img), stream_ptr()),
+          "lars_apply")
+
+
 def grad_aggregate(srcs_dev_ptrs, nsrc, src_fp16, dst, n, scale=1.0, accumulate=False):
     """srcs_dev_ptrs: int64 device tensor holding nsrc device pointers."""
     check(kernels().psx_grad_aggregate(ptr(srcs_dev_ptrs), nsrc, int(src_fp16), ptr(dst),

@@ -50,7 +50,8 @@ def graph_round_enabled(cfg, transport) -> bool:
     # join at the end and the apply running beside the backward kernels; it pays only when the
     # exposed xGMI time of the serial round (reduce 22.4 MB + broadcast 22.5 MB) exceeds that
     return (os.environ.get("PSX_GRAPH_ROUND", "0") == "1" and getattr(transport, "native", False)
-            and cfg.topology == "colocated" and not cfg.momentum and not cfg.bn_sync)
+            and cfg.topology == "colocated" and not cfg.momentum and not cfg.bn_sync
+            and cfg.optimizer != "lars")  # per-bucket applies: a bucket may split a tensor
 
 
 class GraphRoundChannel(SyncCollectiveChannel):

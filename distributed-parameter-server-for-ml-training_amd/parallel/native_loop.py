@@ -73,9 +73,10 @@ def _lib():
 
 
 def native_loop_enabled(cfg, transport) -> bool:
-    """Default for async jobs on the native transport (PSX_NATIVE_LOOP=0: the Python loop)."""
+    """Default for async jobs on the native transport (PSX_NATIVE_LOOP=0: the Python loop). The
+    C++ loop launches the SGD kernels itself: --optimizer lars is served by the Python loop."""
     return (os.environ.get("PSX_NATIVE_LOOP", "1") == "1" and getattr(transport, "native", False)
-            and cfg.codec in ("fp16", "none") and not cfg.bn_sync)
+            and cfg.codec in ("fp16", "none") and not cfg.bn_sync and cfg.optimizer != "lars")
 
 
 class NativeServerLoop:
@@ -91,6 +92,8 @@ class NativeServerLoop:
         self.rank_of_wid = dict(rank_of_wid)
         lay = server.layout
         cfg = server.cfg
+        if cfg.optimizer == "lars":  # csrc/server/event_loop.cpp launches psx_sgd_apply itself
+            raise ValueError("the native event loop applies plain SGD: --optimizer lars runs on the Python server loop")
         self.small_idx = small_index_of(lay).to(server.device)
         max_wid = max([expected] + [w + 1 for w in rank_of_wid])
         self.max_wid = max_wid

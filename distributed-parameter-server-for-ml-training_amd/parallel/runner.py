@@ -142,6 +142,9 @@ def run_local_threads(cfg, steps: int, log=print, emit: bool = True) -> dict:
     more per worker on the threads, timed. Returns the server metrics plus the timed region's
     processed / accepted pushes and images per second counted over ACCEPTED pushes only."""
     assert cfg.mode == "async"
+    if cfg.optimizer == "lars":
+        raise ValueError("run_local_threads is bound to the native event loop, which applies plain SGD: "
+                         "--optimizer lars is not available here")
     cfg.resolve_overlap(1)
     device = _device_for(0)
     W = cfg.workers

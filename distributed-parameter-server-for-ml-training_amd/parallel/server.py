@@ -64,6 +64,18 @@ class ParameterServer:
         self.momentum_buf = torch.zeros_like(self.params) if cfg.momentum else None
         self._mom_first = True
         self.agg = None  # fp32 aggregation buffer for in-process sync rounds
+        # --optimizer lars: every whole-arena update goes through _lars_update (the LARS pair of
+        # csrc/kernels/lars.hip, staged through agg); its only state is the momentum buffer
+        self._lars = cfg.optimizer == "lars"
+        self._lars_tab = None      # device segment table + scratch (ops/kernels.py LarsTable)
+        self._lars_ratios = None   # CPU arena: the last update's trust ratios of the adapted tensors
+        self._lars_applied = False
+        if self._lars:
+            self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+            if self.device.type == "cuda":
+                from ..ops import kernels as K
+
+                self._lars_tab = K.lars_table(layout, self.device)
         self.wire = None  # WeightWire fetch payload kept current by the apply (enable_weight_wire)
         self._wire_stale = False
         self._pending = {}
@@ -84,7 +96,7 @@ class ParameterServer:
         trace.mark("psx.apply")
         t0 = self._time_begin()
         if grads.dtype == torch.int32:  # top-k payload (parallel/topk.py)
-            if not self.cfg.momentum and not self.cfg.weight_decay:
+            if not self.cfg.momentum and not self.cfg.weight_decay and not self._lars:
                 # no optimizer state: scatter straight into the fp32 master parameters
                 topk.decode_add(grads, self.params, -self.lr * weight, self._kcap)
                 self._wire_stale = True  # the bf16 image was not written by this update
@@ -99,8 +111,9 @@ class ParameterServer:
     def _apply_q8(self, payloads: list, weight: float):
         """The update from q8 payloads, decoded and summed in fp32 in list order: one fused
         launch on the device (the weight image, when enabled, written in the same pass); the
-        torch decode into the aggregation buffer on a CPU arena."""
-        if self.device.type == "cuda":
+        torch decode into the aggregation buffer on a CPU arena. LARS: decoded into the
+        aggregation buffer on either, then the dense entry of the LARS pair."""
+        if self.device.type == "cuda" and not self._lars:
             from ..ops import kernels as K
 
             img = self.wire.img[: self.n] if self.wire is not None else None
@@ -174,6 +187,9 @@ class ParameterServer:
         """The update restricted to params[lo:hi] (g holds exactly that slice): one bucket of a
         backward-overlapped sync round (parallel/overlap.py). Several ranges of one round share
         the same momentum 'first step' flag; finish_round_apply closes the round."""
+        if self._lars:
+            self._lars_whole(lo, hi)
+            return self._lars_update([g], weight)
         p = self.params[lo:hi]
         buf = self.momentum_buf[lo:hi] if self.momentum_buf is not None else None
         if self.device.type == "cuda":
@@ -199,6 +215,9 @@ class ParameterServer:
     def apply_range_sources(self, srcs: list, weight: float, lo: int, hi: int):
         """apply_range of the fp32 sum of several wires' [lo:hi] (fixed list order): one bucket
         of an overlapped round whose wires were gathered (parallel/overlap.py)."""
+        if self._lars:
+            self._lars_whole(lo, hi)
+            return self._lars_update(list(srcs), weight)
         if self.device.type == "cuda":
             from ..ops import kernels as K
 
@@ -212,6 +231,76 @@ class ParameterServer:
         for s in srcs:  # fixed order, fp32 accumulation
             agg.add_(s[lo:hi].to(torch.float32))
         self.apply_range(agg, weight, lo, hi)
+
+    # ------------------------------------------------------------------ LARS (--optimizer lars)
+    def _lars_whole(self, lo: int, hi: int):
+        if (lo, hi) != (0, self.n):
+            raise ValueError(f"--optimizer lars needs every tensor's norm before its first element moves: a partial "
+                             f"range [{lo}, {hi}) of {self.n} cannot be applied (no bucketed or sharded updates)")
+
+    def _lars_update(self, srcs: list, weight: float):
+        """The whole-arena LARS update from dense wires (fp16 / fp32, summed in fp32 in list
+        order) or from the aggregation buffer itself (a decoded or accumulated sum):
+        d = lambda_t * (weight * s + wd * w) for tensors with ndim > 1, lambda_t = trust * |w| /
+        (weight * |s| + wd * |w| + eps) (1 when a norm is 0); d = weight * s for 1-D tensors;
+        then the momentum form of apply_range. Device: the two launches of csrc/kernels/lars.hip;
+        CPU arena: the same formula in torch, tensor by tensor (equal to a tolerance, not bit for
+        bit: the reduction orders differ)."""
+        cfg = self.cfg
+        self._lars_applied = True
+        staged = len(srcs) == 1 and srcs[0].dtype == torch.float32 and srcs[0].data_ptr() == self.agg.data_ptr()
+        if self.device.type == "cuda":
+            from ..ops import kernels as K
+
+            kw = dict(lr=self.lr, gscale=weight, momentum=cfg.momentum, wd=cfg.weight_decay, trust=cfg.lars_trust,
+                      eps=cfg.lars_eps, buf=self.momentum_buf, first=self._mom_first, n=self.n,
+                      img=self.wire.img[: self.n] if self.wire is not None else None)
+            if staged:
+                K.lars_apply(self.params, self.agg, self._lars_tab, **kw)
+            else:
+                K.lars_apply_multi(self.params, [s[: self.n] for s in srcs], self.agg, self._lars_tab, **kw)
+            return
+        if not staged:
+            self.agg.zero_()
+            for s in srcs:  # fixed order, fp32 accumulation
+                self.agg.add_(s[: self.n].to(torch.float32))
+        if self.wire is not None:
+            self._wire_stale = True
+        ratios = []
+        for e in self.layout.entries.values():
+            if e.region != "param" or not e.numel:
+                continue
+            w = self.params[e.offset:e.offset + e.numel]
+            d = self.agg[e.offset:e.offset + e.numel] * weight
+            if len(e.shape) > 1:
+                wn, gn = float(w.double().norm()), float(d.double().norm())
+                lam = cfg.lars_trust * wn / (gn + cfg.weight_decay * wn + cfg.lars_eps) if wn > 0 and gn > 0 else 1.0
+                ratios.append(lam)
+                if cfg.weight_decay:
+                    d = d + cfg.weight_decay * w
+                d = d * lam
+            if self.momentum_buf is not None:
+                buf = self.momentum_buf[e.offset:e.offset + e.numel]
+                if self._mom_first:
+                    buf.copy_(d)
+                else:
+                    buf.mul_(cfg.momentum).add_(d)
+                d = buf
+            w.sub_(self.lr * d)
+        self._lars_ratios = ratios
+
+    def lars_trust_ratios(self):
+        """{min, median, max} of the last update's trust ratios over the adapted tensors (read
+        from the device ratio table here, not per round); None before the first update."""
+        if not self._lars_applied:
+            return None
+        if self._lars_tab is not None:
+            r = self._lars_tab.ratios.cpu()[torch.tensor(self._lars_tab.adapt)]
+        else:
+            r = torch.tensor(self._lars_ratios)
+        if not r.numel():
+            return None
+        return {"min": float(r.min()), "median": float(r.median()), "max": float(r.max())}
 
     def finish_round_apply(self, dt: float = -1.0):
         """Closes one update (global_step + 1). ``dt`` >= 0: its host-measured time (CPU arena);
@@ -406,7 +495,9 @@ class ParameterServer:
             return False
         trace.mark("psx.apply")
         t0 = self._time_begin()
-        if self.device.type == "cuda":
+        if self._lars:
+            self._lars_update(list(srcs), res.weight)
+        elif self.device.type == "cuda":
             from ..ops import kernels as K
 
             img = self.wire.img[: self.n] if self.wire is not None else None
@@ -497,6 +588,9 @@ class ParameterServer:
             self._drain_update_times(block=True)
         m = self.core.metrics()
         m["update_time_source"] = self.update_time_source
+        m["optimizer"] = self.cfg.optimizer
+        if self._lars:
+            m["lars_trust_ratio"] = self.lars_trust_ratios()
         m["bytes_pushed"] = int(self.bytes_pushed)
         m["bytes_fetched"] = int(self.bytes_fetched)
         if self.images_processed:

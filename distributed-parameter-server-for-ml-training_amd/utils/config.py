@@ -10,7 +10,8 @@ Keeps every flag and environment variable of the reference with the same default
           --epochs 3, --batch-size 128, --lr 0.1, --sync-steps 1
 
 and adds the MI355X-native knobs: --gpus/--nproc, --codec, --topk-ratio,
---dtype, --momentum/--weight-decay (server optimizer, default 0 = reference parity), --model,
+--dtype, --momentum/--weight-decay (server optimizer, default 0 = reference parity),
+--optimizer {sgd,lars} with --lars-trust/--lars-eps, --model,
 --synthetic, --ckpt-every/--resume, --sync-semantics {barrier,reference}, --topology.
 Precedence: explicit CLI flag > JSON config file (--config) > environment > default.
 """
@@ -57,6 +58,13 @@ class PSConfig:
     dtype: str = "fp32"
     momentum: float = 0.0          # server optimizer (0 = reference plain SGD, server.py:133)
     weight_decay: float = 0.0
+    # server optimizer: sgd (the flat update above) | lars (layer-wise adaptive: every tensor with
+    # ndim > 1 gets the trust ratio lars_trust * |w| / (|g| + wd |w| + lars_eps) and the weight
+    # decay, 1-D tensors neither; csrc/kernels/lars.hip). Runs on the Python server's whole-arena
+    # updates only: no native loops, graph round, bucketed overlap or sharded server.
+    optimizer: str = "sgd"
+    lars_trust: float = 0.001
+    lars_eps: float = 1e-8
     sync_semantics: str = "barrier"  # barrier (wait-for-N) | reference (count-triggered)
     # The reference server never updates BN running statistics and every fetch overwrites the
     # workers' copies (server.py:96,131-133 + worker.py:252), so evaluation runs on near-initial
@@ -115,6 +123,15 @@ class PSConfig:
             raise ValueError(f"--codec must be none, fp16, q8 or topk, got {self.codec!r}")
         if self.topology not in ("colocated", "dedicated", "sharded"):
             raise ValueError(f"--topology must be colocated, dedicated or sharded, got {self.topology!r}")
+        if self.optimizer not in ("sgd", "lars"):
+            raise ValueError(f"--optimizer must be sgd or lars, got {self.optimizer!r}")
+        if self.optimizer == "lars":
+            if not (self.lars_trust > 0.0) or self.lars_eps < 0.0:
+                raise ValueError("--optimizer lars: --lars-trust must be > 0 and --lars-eps >= 0")
+            if self.topology == "sharded":  # a shard boundary may split a tensor
+                raise ValueError("--optimizer lars needs whole tensors on one server: not with --topology sharded")
+            if self.overlap is True:  # a gradient bucket may split a tensor
+                raise ValueError("--optimizer lars updates the whole arena at once: not with --overlap")
         if self.topology == "sharded":  # parallel/sharded.py scope
             if self.mode != "sync" or self.codec not in ("fp16", "none") or self.bn_sync or self.ckpt_every \
                     or self.resume or max(1, self.sync_steps) != 1 or self.overlap is True:
@@ -152,10 +169,11 @@ class PSConfig:
     def resolve_overlap(self, world: int) -> bool:
         """--overlap / --no-overlap, or auto: bucketed rounds when there are peers to exchange
         with and the round qualifies (sync, one push per batch, dense wire, rank-0 server). The
-        error-feedback codecs (q8, topk) encode the whole gradient at once: no bucketed rounds."""
+        error-feedback codecs (q8, topk) encode the whole gradient at once, and --optimizer lars
+        needs every tensor's norm before its first element moves: no bucketed rounds."""
         if self.overlap is None:
             self.overlap = (world > 1 and self.mode == "sync" and max(1, self.sync_steps) == 1
-                            and self.dense_wire and self.topology != "sharded")
+                            and self.dense_wire and self.topology != "sharded" and self.optimizer != "lars")
         return bool(self.overlap)
 
     @property
@@ -193,6 +211,11 @@ def add_arguments(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
       help="worker compute precision: fp32 (reference, default) or bf16 (fast path)")
     A("--momentum", type=float, default=None)
     A("--weight-decay", type=float, default=None)
+    A("--optimizer", choices=["sgd", "lars"], default=None,
+      help="server optimizer: sgd (default) or lars (layer-wise trust ratio on tensors with ndim > 1; "
+           "uses --momentum / --weight-decay; Python server, whole-arena updates)")
+    A("--lars-trust", type=float, default=None, help="LARS trust coefficient (default 0.001)")
+    A("--lars-eps", type=float, default=None, help="LARS denominator epsilon (default 1e-8)")
     A("--sync-semantics", choices=["barrier", "reference"], default=None)
     A("--bn-sync", action="store_true", default=None, help="workers push BN running stats; server averages")
     A("--deterministic", dest="deterministic", action="store_true", default=None,

@@ -13,6 +13,11 @@
 * ``psx_fp32_q8``     the same with the block-scaled int8 wire and error feedback (--codec q8); also
                       compared against ``psx_fp32`` (``q8_vs_psx_fp32`` in the JSON), next to the
                       torch seed-to-seed spread.
+* ``psx_fp32_lars``   psx_fp32 with the layer-wise adaptive server optimizer (--optimizer lars, momentum
+                      0.9, weight decay 5e-4, trust 0.001, lr ``--lars-lr``, default 2.0: the
+                      trust ratio scales every tensor's step to lr * 0.001 * |w| / |g|, so its lr is
+                      not comparable to the SGD curves' 0.05); also compared against ``psx_fp32``
+                      (``lars_vs_psx_fp32``), next to the torch seed-to-seed spread.
 * ``psx_bf16``        the bf16 HIP engine (fast path), fp16 wire, bf16conv fetch.
 * ``psx_fp32_reference_bn`` psx_fp32 with the reference's BN semantics (no --bn-sync): same
                       training curve, but the evaluation runs on never-learned running statistics.
@@ -72,13 +77,14 @@ def batches_for(args):
     return out[: args.steps]
 
 
-def run_psx(args, train, test, dtype: str, codec: str, bn_sync: bool = True):
+def run_psx(args, train, test, dtype: str, codec: str, bn_sync: bool = True, **opt):
     """bn_sync: the worker pushes its BN running statistics with the gradient (W = 1: the server
     keeps the worker's, as a single-process trainer does); without it the reference semantics
-    apply (every fetch resets them to the server's never-updated copy)."""
-    cfg = PSConfig(model="resnet18", mode="sync", workers=1, lr=args.lr, batch_size=args.batch, epochs=10 ** 6,
-                   train_samples=args.train, eval_every=0, verbose=0, dtype=dtype, codec=codec,
-                   bn_sync=bn_sync).validate()
+    apply (every fetch resets them to the server's never-updated copy). ``opt``: server optimizer
+    fields of PSConfig (optimizer, lr, momentum, weight_decay) overriding the plain SGD at --lr."""
+    cfg = PSConfig(**{**dict(model="resnet18", mode="sync", workers=1, lr=args.lr, batch_size=args.batch,
+                             epochs=10 ** 6, train_samples=args.train, eval_every=0, verbose=0, dtype=dtype,
+                             codec=codec, bn_sync=bn_sync), **opt}).validate()
     model, lay, arena, counters = build_state(cfg)
     srv = ParameterServer(cfg, lay, arena.clone(), counters, device=DEV, total_workers=1, log=_noop)
     comp = make_compute(model, lay, args.batch, DEV, "resnet18", _wire_dtype(cfg), seed=0, use_graph=True,
@@ -193,18 +199,25 @@ def main():
     ap.add_argument("--window", type=int, default=25, help="moving-average window of the compared curves")
     ap.add_argument("--out", default="gpurun_out/convergence")
     ap.add_argument("--skip-w4", action="store_true")
+    ap.add_argument("--lars-lr", type=float, default=2.0, help="lr of the psx_fp32_lars curve")
+    ap.add_argument("--only", default="", help="comma-separated subset of the curves to run (default: all)")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     train = DeviceDataset.synthetic_hard(args.train, device=DEV)
     test = DeviceDataset.synthetic_hard(args.test, device=DEV, offset=10_000_000)
     runs = {}
+    lars = dict(optimizer="lars", lr=args.lars_lr, momentum=0.9, weight_decay=5e-4)
+    only = [x for x in args.only.split(",") if x]
     for name, fn in (("torch_fp32", lambda: run_torch(args, train, test, 0)),
                      ("torch_fp32_init1", lambda: run_torch(args, train, test, 1)),
                      ("psx_fp32", lambda: run_psx(args, train, test, "fp32", "fp16")),
                      ("psx_fp32_wire32", lambda: run_psx(args, train, test, "fp32", "none")),
                      ("psx_fp32_q8", lambda: run_psx(args, train, test, "fp32", "q8")),
+                     ("psx_fp32_lars", lambda: run_psx(args, train, test, "fp32", "fp16", **lars)),
                      ("psx_bf16", lambda: run_psx(args, train, test, "bf16", "fp16")),
                      ("psx_fp32_reference_bn", lambda: run_psx(args, train, test, "fp32", "fp16", bn_sync=False))):
+        if only and name not in only and name != "torch_fp32":
+            continue
         runs[name] = fn()
         r = runs[name]
         print(f"{name:18s} last-100 loss {np.mean(r['loss'][-100:]):.4f} test acc {r['test_acc']:.2f}% "
@@ -220,20 +233,27 @@ def main():
                      "last100_loss_diff": float(np.mean(r["loss"][-100:]) - np.mean(runs["torch_fp32"]["loss"][-100:])),
                      "test_acc_diff_pp": r["test_acc"] - runs["torch_fp32"]["test_acc"]}
         print(f"  vs torch_fp32: {name:18s} {json.dumps(cmp[name])}", flush=True)
-    d = smooth(runs["psx_fp32_q8"]["loss"], args.window) - smooth(runs["psx_fp32"]["loss"], args.window)
-    q8cmp = {"max_abs_smoothed_loss_diff": float(np.max(np.abs(d))),
-             "mean_abs_smoothed_loss_diff": float(np.mean(np.abs(d))),
-             "torch_seed_spread_mean_abs": cmp["torch_fp32_init1"]["mean_abs_smoothed_loss_diff"]}
-    print(f"  psx_fp32_q8 vs psx_fp32: {json.dumps(q8cmp)}", flush=True)
+    vs_psx = {}
+    for name in ("psx_fp32_q8", "psx_fp32_lars"):
+        if name not in runs or "psx_fp32" not in runs:
+            continue
+        d = smooth(runs[name]["loss"], args.window) - smooth(runs["psx_fp32"]["loss"], args.window)
+        vs_psx[name] = {"max_abs_smoothed_loss_diff": float(np.max(np.abs(d))),
+                        "mean_abs_smoothed_loss_diff": float(np.mean(np.abs(d))),
+                        "mean_smoothed_loss_diff": float(np.mean(d)),
+                        "torch_seed_spread_mean_abs": cmp.get("torch_fp32_init1", {}).get(
+                            "mean_abs_smoothed_loss_diff")}
+        print(f"  {name} vs psx_fp32: {json.dumps(vs_psx[name])}", flush=True)
     w4 = {}
-    if not args.skip_w4:
+    if not args.skip_w4 and not only:
         for bn in (False, True):
             key = "bn_sync" if bn else "reference_bn_semantics"
             w4[key] = run_w4(args, bn)
             print(f"W=4 {key}: {json.dumps(w4[key])}", flush=True)
     out = {"config": vars(args), "data": "synthetic_hard: 4x4 class prototypes (std 12) + pixel noise (std 64), "
                                           "20% label noise, 100 classes",
-           "runs": runs, "vs_torch_fp32": cmp, "q8_vs_psx_fp32": q8cmp, "w4_sync": w4}
+           "runs": runs, "vs_torch_fp32": cmp, "q8_vs_psx_fp32": vs_psx.get("psx_fp32_q8"),
+           "lars_vs_psx_fp32": vs_psx.get("psx_fp32_lars"), "w4_sync": w4}
     with open(os.path.join(args.out, "convergence_parity.json"), "w") as f:
         json.dump(out, f)
     try:
