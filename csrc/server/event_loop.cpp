@@ -24,6 +24,12 @@
 //             (csrc/kernels/optim.hip); pushes complete in any order across workers. Snapshots are
 //             taken on the same stream, so a fetch never sees a half-applied update and a send
 //             in flight never races the next update (it reads its own snapshot).
+//   delay     --dc-lambda > 0 (csrc/kernels/dcasgd.hip): every fetch also leaves the worker's backup
+//   compens.  of the fp32 parameters (psx_dc_fetch_copy in place of the arena copy, or a
+//             backup-only pass when the snapshot is the bf16 image), and the apply of a worker with
+//             a valid backup is psx_dc_apply. The backup is written and read on the update stream
+//             only, so the ordering rules above are unchanged. With dc_lambda == 0 no launch, copy
+//             or allocation differs.
 //   local     the co-located worker of rank 0 calls psx_loop_local_push / _fetch / _done; the
 //             loop thread serves them between mailbox messages, ordered on the update stream
 //             against the caller's stream by events.
@@ -87,6 +93,9 @@ struct Rt {  // libpsx_runtime.so + libpsx_kernels.so entry points
   long long (*ps_global_step)(void*);
   int (*sgd_apply)(float*, const void*, float*, long, float, float, float, float, int, int, void*, hipStream_t);
   int (*gather_f32)(const float*, const long*, long, float*, hipStream_t);
+  int (*dc_apply)(float*, const void*, const float*, float*, float*, long, float, float, float, float, float, float,
+                  float, int, int, void*, hipStream_t);
+  int (*dc_fetch_copy)(const float*, float*, float*, long, long, hipStream_t);
 };
 
 template <typename F>
@@ -141,6 +150,9 @@ struct PsxLoopCfg {  // mirrored by parallel/native_loop.py (ctypes.Structure)
   const int* comm_owned;   // worker id -> 1: comms[w] is w's own pair communicator (abortable)
   double transfer_timeout;  // s, 0 = off: a receive / snapshot send in flight longer drops the worker
   double stall_timeout;     // s, 0 = off: a remote worker without any request that long is dropped
+  // delay compensation (--dc-lambda, csrc/kernels/dcasgd.hip); dc_lambda == 0: off, nothing below is used
+  float dc_lambda, dc_decay, dc_eps;
+  float* dc_ms;             // device mean-square buffer [n_params] (nullptr: the constant form)
 };
 
 struct PsxLoop {
@@ -161,6 +173,11 @@ struct PsxLoop {
   std::vector<float*> snap_small;  // fp32 remainder (bf16conv) or the whole arena (fp32 fetch)
   std::vector<hipEvent_t> sent;  // per worker: last snapshot send done (snapshot reusable)
   std::vector<double> sent_t;    // per worker: when that send was posted
+  // delay compensation: per worker, the parameters as of its last fetch (written by the fetch and
+  // read by the apply, both on s_upd only) and whether a fetch has filled it
+  std::vector<float*> bak;
+  std::vector<char> bak_valid;
+  long long dc_comp = 0, dc_uncomp = 0;  // applies with / without a valid backup
   struct Pending {
     int wid;
     long long local_step;
@@ -245,7 +262,25 @@ int alloc_worker(PsxLoop* L, int w) {
 
 // the fused SGD apply of one gradient with the core's weight (+ the bf16 image of the updated
 // state when the fetch payload carries it; the fp32 fetch never reads one)
-int apply(PsxLoop* L, const void* g, float weight) {
+// the worker's backup buffer (delay compensation), allocated at its first fetch
+int alloc_backup(PsxLoop* L, int w) {
+  if (L->bak[w]) return 0;
+  return hipMalloc((void**)&L->bak[w], (size_t)L->c.n_params * 4) == hipSuccess ? 0 : -27;
+}
+
+// Delay compensation on: the fetch of worker w leaves its backup. dst (nullable) also receives the
+// whole fp32 arena from the same read; both on the update stream.
+int fetch_backup(PsxLoop* L, int w, float* dst) {
+  if (int e = alloc_backup(L, w)) return e;
+  (void)hipGetLastError();  // see apply()
+  if (L->rt.dc_fetch_copy(L->c.arena, dst, L->bak[w], dst ? L->c.arena_numel : L->c.n_params, L->c.n_params,
+                          L->s_upd))
+    return -28;
+  L->bak_valid[w] = 1;
+  return 0;
+}
+
+int apply(PsxLoop* L, const void* g, float weight, int wid) {
   read_timings(L, false);
   std::pair<hipEvent_t, hipEvent_t> tp{nullptr, nullptr};
   if (!L->tfree.empty()) {
@@ -259,8 +294,17 @@ int apply(PsxLoop* L, const void* g, float weight) {
   // the kernel wrappers report hipGetLastError(): clear what an earlier hipEventQuery (a
   // hipErrorNotReady of a transfer still in flight) left in this thread's error slot
   (void)hipGetLastError();
-  const int e = L->rt.sgd_apply(L->c.arena, g, L->c.mom_buf, L->c.n_params, L->c.lr, weight, L->c.momentum,
-                                L->c.weight_decay, L->c.mom_first, L->c.grad_fp16, L->img, L->s_upd);
+  int e;
+  const bool dc = L->c.dc_lambda > 0.f;
+  const bool valid = dc && wid >= 0 && wid < L->c.max_wid && L->bak[wid] && L->bak_valid[wid];
+  if (dc) ++(valid ? L->dc_comp : L->dc_uncomp);
+  if (dc && (valid || L->c.dc_ms))  // no backup: uncompensated (the adaptive form still updates ms)
+    e = L->rt.dc_apply(L->c.arena, g, valid ? L->bak[wid] : nullptr, L->c.dc_ms, L->c.mom_buf, L->c.n_params, L->c.lr,
+                       weight, L->c.momentum, L->c.weight_decay, L->c.dc_lambda, L->c.dc_decay, L->c.dc_eps,
+                       L->c.mom_first, L->c.grad_fp16, L->img, L->s_upd);
+  else
+    e = L->rt.sgd_apply(L->c.arena, g, L->c.mom_buf, L->c.n_params, L->c.lr, weight, L->c.momentum,
+                        L->c.weight_decay, L->c.mom_first, L->c.grad_fp16, L->img, L->s_upd);
   PSX_HIP(L, hipEventRecord(tp.second, L->s_upd));
   L->tbusy.push_back(tp);
   L->c.mom_first = 0;
@@ -319,10 +363,15 @@ int serve_fetch(PsxLoop* L, int w, int rank) {
   // snapshot on the update stream (after every apply so far), once the previous send of this
   // worker's snapshot has finished
   PSX_HIP(L, hipStreamWaitEvent(L->s_upd, L->sent[w], 0));
-  if (L->c.fetch_fp32) {
+  const bool dc = L->c.dc_lambda > 0.f;
+  if (L->c.fetch_fp32 && dc) {  // snapshot + backup from one read of the arena
+    if (int e = fetch_backup(L, w, L->snap_small[w])) return e;
+  } else if (L->c.fetch_fp32) {
     PSX_HIP(L, hipMemcpyAsync(L->snap_small[w], L->c.arena, (size_t)L->c.arena_numel * 4, hipMemcpyDeviceToDevice,
                               L->s_upd));
   } else {
+    if (dc)  // the snapshot is the bf16 image, not the fp32 arena: a backup-only pass
+      if (int e = fetch_backup(L, w, nullptr)) return e;
     PSX_HIP(L, hipMemcpyAsync(L->snap_img[w], L->img, (size_t)L->c.n_params * 2, hipMemcpyDeviceToDevice, L->s_upd));
     (void)hipGetLastError();  // see apply()
     if (L->c.small_n && L->rt.gather_f32(L->c.arena, L->c.small_idx, L->c.small_n, L->snap_small[w], L->s_upd))
@@ -403,7 +452,7 @@ void complete_pending(PsxLoop* L) {
     int accepted = 0;
     if (d == PSX_APPLY) {
       PSX_HIP(L, hipStreamWaitEvent(L->s_upd, p.ev, 0));
-      if (apply(L, L->slot[p.wid], weight)) L->err = -30;
+      if (apply(L, L->slot[p.wid], weight, p.wid)) L->err = -30;
       accepted = 1;
     }
     L->rt.mbox_reply(L->c.mbox, L->c.remote_rank[p.wid], R_PUSHED, p.wid, accepted,
@@ -428,7 +477,7 @@ void serve_local(PsxLoop* L) {
       const bool same = r->stream == L->s_upd;
       if (d == PSX_APPLY) {
         if (!same) stream_after(L, L->s_upd, r->stream);
-        if (apply(L, r->grads, weight)) L->err = -31;
+        if (apply(L, r->grads, weight, r->wid)) L->err = -31;
         r->accepted = 1;
       }
       r->staleness = st;
@@ -438,8 +487,12 @@ void serve_local(PsxLoop* L) {
       r->global_step = L->rt.ps_on_fetch(L->c.core, r->wid, now_s());
       const bool same = r->stream == L->s_upd;
       if (!same) stream_after(L, L->s_upd, r->stream);
-      PSX_HIP(L, hipMemcpyAsync(r->dst, L->c.arena, (size_t)L->c.arena_numel * 4, hipMemcpyDeviceToDevice,
-                                L->s_upd));
+      if (L->c.dc_lambda > 0.f && r->wid >= 0 && r->wid < L->c.max_wid) {
+        if (fetch_backup(L, r->wid, r->dst)) L->err = -34;
+      } else {
+        PSX_HIP(L, hipMemcpyAsync(r->dst, L->c.arena, (size_t)L->c.arena_numel * 4, hipMemcpyDeviceToDevice,
+                                  L->s_upd));
+      }
       if (!same) stream_after(L, r->stream, L->s_upd);
     } else {
       L->rt.ps_job_finished(L->c.core, r->wid);
@@ -592,7 +645,8 @@ void* psx_loop_create(const PsxLoopCfg* cfg, const char* runtime_path, const cha
                   bind(rt, "psx_ps_job_finished", &r.ps_job_finished) && bind(rt, "psx_ps_mark_dead", &r.ps_mark_dead) &&
                   bind(rt, "psx_ps_check_timeouts", &r.ps_check_timeouts) &&
                   bind(rt, "psx_ps_global_step", &r.ps_global_step) && bind(kn, "psx_sgd_apply", &r.sgd_apply) &&
-                  bind(kn, "psx_gather_f32", &r.gather_f32);
+                  bind(kn, "psx_gather_f32", &r.gather_f32) && bind(kn, "psx_dc_apply", &r.dc_apply) &&
+                  bind(kn, "psx_dc_fetch_copy", &r.dc_fetch_copy);
   if (!ok) {
     delete L;
     return nullptr;
@@ -604,6 +658,8 @@ void* psx_loop_create(const PsxLoopCfg* cfg, const char* runtime_path, const cha
   L->snap_small.assign(n, nullptr);
   L->sent.assign(n, nullptr);
   L->sent_t.assign(n, 0.0);
+  L->bak.assign(n, nullptr);
+  L->bak_valid.assign(n, 0);
   L->ws.assign(n, PsxLoop::WState{});
   return L;
 }
@@ -622,6 +678,12 @@ int psx_loop_join(void* h) {
 }
 
 long long psx_loop_applies(void* h) { return ((PsxLoop*)h)->applies; }
+
+// Delay compensation: out = [applies with a valid backup, applies without one].
+void psx_loop_dc_counts(void* h, long long* out) {
+  out[0] = ((PsxLoop*)h)->dc_comp;
+  out[1] = ((PsxLoop*)h)->dc_uncomp;
+}
 
 // After join: the dropped workers (ids into out[cap]) and, per id, whether their pair
 // communicator was aborted by the loop (aborted[cap], nullable: the caller must not destroy it).
@@ -680,6 +742,8 @@ void psx_loop_destroy(void* h) {
   PsxLoop* L = (PsxLoop*)h;
   if (!L) return;
   if (L->th.joinable()) L->th.join();
+  for (float* b : L->bak)  // touched on the update stream only, which the loop drained
+    if (b) hipFree(b);
   for (size_t w = 0; w < L->slot.size(); ++w) {
     if (L->ws[w].dead && L->s_comm[w] && hipStreamQuery(L->s_comm[w]) == hipErrorNotReady) {
       // a dropped worker's transfer never completed: keep its buffers (a late kernel may still

@@ -699,6 +699,45 @@ def lars_apply(p, stage, table: LarsTable, lr, gscale=1.0, momentum=0.0, wd=0.0,
           "lars_apply")
 
 
+def _dc_f32(t, n, dev, what):
+    assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n and t.device == dev, what
+
+
+def dc_apply(p, g, bak, lr, lam, ms=None, decay=0.95, eps=1e-7, gscale=1.0, momentum=0.0, wd=0.0, buf=None,
+             first=False, n=None, img=None):
+    """The delay-compensated server update of one async push (csrc/kernels/dcasgd.hip), one pass:
+    g~ = g + lam' * g * g * (p - bak); p -= lr*(gscale*g~ + wd*p) [momentum]. ``ms`` None: the
+    constant form, lam' = lam; else ms = decay*ms + (1-decay)*g*g and lam' = lam / sqrt(ms + eps).
+    ``bak`` None: a push without a backup, g~ = g (ms is still updated). g: fp16 or fp32."""
+    n = p.numel() if n is None else n
+    assert n > 0 and p.device.type == "cuda", "dc_apply device"
+    _dc_f32(p, n, p.device, "dc_apply p")
+    assert g.dtype in (torch.float16, torch.float32) and g.is_contiguous() and g.numel() >= n \
+        and g.device == p.device, "dc_apply g"
+    for t, what in ((bak, "bak"), (ms, "ms"), (buf, "buf")):
+        if t is not None:
+            _dc_f32(t, n, p.device, f"dc_apply {what}")
+    if img is not None:
+        assert img.dtype == torch.bfloat16 and img.is_contiguous() and img.numel() >= n and img.device == p.device, \
+            "dc_apply img"
+    check(kernels().psx_dc_apply(ptr(p), ptr(g), ptr(bak), ptr(ms), ptr(buf), n, float(lr), float(gscale),
+                                 float(momentum), float(wd), float(lam), float(decay), float(eps), int(first),
+                                 int(g.dtype == torch.float16), ptr(img), stream_ptr()), "dc_apply")
+
+
+def dc_fetch_copy(src, dst, bak, n_params=None):
+    """dst[:] = src (``dst`` None: skipped) and bak[:n_params] = src[:n_params] from one read of
+    the fp32 arena ``src``: the fetch that also leaves the worker's delay-compensation backup."""
+    n_arena = src.numel()
+    n_params = n_arena if n_params is None else int(n_params)
+    assert 0 <= n_params <= n_arena and src.device.type == "cuda", "dc_fetch_copy range"
+    _dc_f32(src, n_arena, src.device, "dc_fetch_copy src")
+    _dc_f32(bak, n_params, src.device, "dc_fetch_copy bak")
+    if dst is not None:
+        _dc_f32(dst, n_arena, src.device, "dc_fetch_copy dst")
+    check(kernels().psx_dc_fetch_copy(ptr(src), ptr(dst), ptr(bak), n_arena, n_params, stream_ptr()), "dc_fetch_copy")
+
+
 def grad_aggregate(srcs_dev_ptrs, nsrc, src_fp16, dst, n, scale=1.0, accumulate=False):
     """srcs_dev_ptrs: int64 device tensor holding nsrc device pointers."""
     check(kernels().psx_grad_aggregate(ptr(srcs_dev_ptrs), nsrc, int(src_fp16), ptr(dst),

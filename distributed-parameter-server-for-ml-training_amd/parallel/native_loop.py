@@ -14,7 +14,9 @@ before, tensors by ncclSend/ncclRecv on their pair communicator (parallel/rccl.p
 posted on a communication stream ordered after the worker's compute stream by events.
 
 Scope: dense fp16/fp32 gradients; SGD with the server's momentum / weight decay; fetch payload
-bf16conv or fp32; checkpoints. Not covered (Python loop): top-k payloads, --bn-sync.
+bf16conv or fp32; checkpoints; delay compensation (--dc-lambda: the loop keeps the per-worker
+backups itself and launches csrc/kernels/dcasgd.hip). Not covered (Python loop): top-k / q8
+payloads, --bn-sync.
 """
 from __future__ import annotations
 
@@ -43,7 +45,7 @@ class LoopCfg(C.Structure):
                 ("expected", i32), ("fetch_fp32", i32), ("mom_first", i32), ("mom_buf", vp),
                 ("heartbeat_timeout", f64), ("poll_s", f64), ("upd_stream", vp), ("own_upd_stream", i32),
                 ("ckpt_every", C.c_longlong), ("ckpt_cb", CKPT_CB), ("comm_owned", vp), ("transfer_timeout", f64),
-                ("stall_timeout", f64)]
+                ("stall_timeout", f64), ("dc_lambda", f32), ("dc_decay", f32), ("dc_eps", f32), ("dc_ms", vp)]
 
 
 _SIGS = {
@@ -52,6 +54,7 @@ _SIGS = {
     "psx_loop_start": (i32, [vp]),
     "psx_loop_join": (i32, [vp]),
     "psx_loop_applies": (C.c_longlong, [vp]),
+    "psx_loop_dc_counts": (None, [vp, C.POINTER(C.c_longlong)]),
     "psx_loop_dropped": (i32, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), i32]),
     "psx_loop_local_push": (i32, [vp, i32, vp, C.c_longlong, vp, C.POINTER(C.c_longlong)]),
     "psx_loop_local_fetch": (C.c_longlong, [vp, i32, vp, vp]),
@@ -128,7 +131,10 @@ class NativeServerLoop:
                            own_upd_stream=int(update_stream is None),
                            ckpt_every=int(cfg.ckpt_every or 0) if cfg.ckpt_dir else 0, ckpt_cb=self._ckpt,
                            comm_owned=C.cast(self.owned, vp), transfer_timeout=float(cfg.transfer_timeout or 0.0),
-                           stall_timeout=float(cfg.stall_timeout or 0.0))
+                           stall_timeout=float(cfg.stall_timeout or 0.0),
+                           dc_lambda=float(cfg.dc_lambda) if server._dc else 0.0, dc_decay=float(cfg.dc_decay),
+                           dc_eps=float(cfg.dc_eps),
+                           dc_ms=server._dc_ms.data_ptr() if server._dc_ms is not None else None)
         kernels()  # both libraries are loaded (the loop binds their entry points by path)
         runtime()
         self.h = _lib().psx_loop_create(C.byref(self.cfg), os.path.join(NATIVE_DIR, "libpsx_runtime.so").encode(),
@@ -171,6 +177,11 @@ class NativeServerLoop:
         s._mom_first = s._mom_first and not applies
         if applies:  # the loop fed each apply's device time to the core (event_loop.cpp read_timings)
             s.update_time_source = "device events around the apply kernels (native loop)"
+        if s._dc:  # the loop kept the backups and counted the applies with / without one
+            dc = (C.c_longlong * 2)()
+            _lib().psx_loop_dc_counts(self.h, dc)
+            s.dc_compensated += int(dc[0])
+            s.dc_uncompensated += int(dc[1])
         s.bytes_pushed = int(s.core.metrics().get("gradients_processed", 0)) * s.n * (2 if s.cfg.codec == "fp16" else 4)
         _lib().psx_loop_destroy(self.h)
         self.h = None

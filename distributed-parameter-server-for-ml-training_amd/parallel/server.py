@@ -76,6 +76,17 @@ class ParameterServer:
                 from ..ops import kernels as K
 
                 self._lars_tab = K.lars_table(layout, self.device)
+        # --dc-lambda (async): delay compensation (csrc/kernels/dcasgd.hip). Every fetch leaves the
+        # worker's backup of the fp32 parameters (note_fetch); the apply of a push from a worker
+        # with a valid backup is g + lam * g * g * (w - bak) in place of g (_apply_dc).
+        self._dc = cfg.dc_lambda > 0 and cfg.mode == "async"
+        self._dc_bak = {}          # worker id -> fp32 [n] backup, allocated at the worker's first fetch
+        self._dc_valid = set()     # worker ids whose backup holds their last fetch
+        self._dc_ms = None         # --dc-adaptive: running mean square of the gradients, fp32 [n]
+        self.dc_compensated = 0
+        self.dc_uncompensated = 0
+        if self._dc and cfg.dc_adaptive:
+            self._dc_ms = torch.zeros(self.n, dtype=torch.float32, device=self.device)
         self.wire = None  # WeightWire fetch payload kept current by the apply (enable_weight_wire)
         self._wire_stale = False
         self._pending = {}
@@ -90,11 +101,15 @@ class ParameterServer:
             self.resume(cfg.resume)
 
     # ------------------------------------------------------------------ numerics
-    def apply(self, grads: torch.Tensor, weight: float):
+    def apply(self, grads: torch.Tensor, weight: float, worker_id: int | None = None):
         """p <- p - lr * (weight * g [+ wd p]) [momentum]; grads are fp16 wire, fp32, or a top-k
-        (int32) / q8 (uint8) payload."""
+        (int32) / q8 (uint8) payload. ``worker_id``: the pushing worker of an async push (delay
+        compensation reads its backup)."""
         trace.mark("psx.apply")
         t0 = self._time_begin()
+        if self._dc:
+            self._apply_dc(grads, weight, worker_id)
+            return self.finish_round_apply(self._time_end(t0))
         if grads.dtype == torch.int32:  # top-k payload (parallel/topk.py)
             if not self.cfg.momentum and not self.cfg.weight_decay and not self._lars:
                 # no optimizer state: scatter straight into the fp32 master parameters
@@ -123,6 +138,69 @@ class ParameterServer:
         for i, p in enumerate(payloads):
             self._dense_of(p, add=i > 0)
         self.apply_range(self.agg, weight, 0, self.n)
+
+    # ------------------------------------------------------------------ delay compensation (--dc-lambda)
+    def note_fetch(self, worker_id: int, dst: torch.Tensor | None = None) -> int:
+        """Worker ``worker_id`` fetches the current state: the core's bookkeeping and, with delay
+        compensation on, the worker's backup of the fp32 parameters, taken in stream order with
+        the applies. ``dst`` (optional, the worker's fp32 arena) also receives the arena — on the
+        device from the same read as the backup (kernels.dc_fetch_copy). Returns the global step."""
+        gs = self.core.on_fetch(worker_id)
+        if not self._dc:
+            if dst is not None:
+                dst.copy_(self.arena)
+            return gs
+        bak = self._dc_bak.get(worker_id)
+        if bak is None:
+            bak = self._dc_bak[worker_id] = torch.empty(self.n, dtype=torch.float32, device=self.device)
+        fused = (self.device.type == "cuda" and (dst is None or (
+            dst.dtype == torch.float32 and dst.device == self.arena.device and dst.is_contiguous()
+            and dst.numel() == self.arena.numel())))
+        if fused:
+            from ..ops import kernels as K
+
+            K.dc_fetch_copy(self.arena, dst, bak, self.n)
+        else:
+            bak.copy_(self.params)
+            if dst is not None:
+                dst.copy_(self.arena)
+        self._dc_valid.add(worker_id)
+        return gs
+
+    def _apply_dc(self, grads: torch.Tensor, weight: float, worker_id):
+        """The delay-compensated update of one async push: g~ = g + lam * g * g * (w - bak), lam =
+        dc_lambda or dc_lambda / sqrt(ms + dc_eps) (adaptive; ms = decay * ms + (1 - decay) * g * g
+        on every apply), then the usual tail. q8 / top-k payloads are decoded into the aggregation
+        buffer first. A worker without a valid backup (no fetch yet, or after a resume) is applied
+        uncompensated and counted. Device: one launch of csrc/kernels/dcasgd.hip; CPU arena: the
+        same formula in torch (equal to a tolerance, not bit for bit)."""
+        cfg = self.cfg
+        bak = self._dc_bak.get(worker_id) if worker_id in self._dc_valid else None
+        if bak is None:
+            self.dc_uncompensated += 1
+        else:
+            self.dc_compensated += 1
+        if grads.dtype in (torch.int32, torch.uint8):
+            grads = self._dense_of(grads)
+        g = grads[: self.n]
+        if bak is None and self._dc_ms is None:  # nothing of the DC form is left: the plain update
+            return self.apply_range(g, weight, 0, self.n)
+        if self.device.type == "cuda":
+            from ..ops import kernels as K
+
+            img = self.wire.img[: self.n] if self.wire is not None else None
+            K.dc_apply(self.params, g, bak, self.lr, cfg.dc_lambda, ms=self._dc_ms, decay=cfg.dc_decay,
+                       eps=cfg.dc_eps, gscale=weight, momentum=cfg.momentum, wd=cfg.weight_decay,
+                       buf=self.momentum_buf, first=self._mom_first, n=self.n, img=img)
+            return
+        g = g.to(torch.float32)
+        lam = cfg.dc_lambda
+        if self._dc_ms is not None:
+            self._dc_ms.mul_(cfg.dc_decay).add_((1.0 - cfg.dc_decay) * g * g)
+            lam = cfg.dc_lambda / torch.sqrt(self._dc_ms + cfg.dc_eps)
+        if bak is not None:
+            g = g + lam * g * g * (self.params - bak)
+        self.apply_range(g, weight, 0, self.n)
 
     # ------------------------------------------------------------------ update timing
     # The reference times the apply itself (server.py:128,140-141) into average_update_time_seconds.
@@ -334,7 +412,7 @@ class ParameterServer:
         return wid, self.total_workers
 
     def fetch_parameters(self, worker_id: int):
-        gs = self.core.on_fetch(worker_id)
+        gs = self.note_fetch(worker_id)
         self.bytes_fetched += self.arena.numel() * 4
         return self.arena, gs
 
@@ -363,7 +441,7 @@ class ParameterServer:
         return self.wire
 
     def fetch_wire(self, worker_id: int, publish_small: bool = True):
-        gs = self.core.on_fetch(worker_id)
+        gs = self.note_fetch(worker_id)
         w = self.wire_for_fetch(publish_small)
         self.bytes_fetched += w.nbytes
         return w, gs
@@ -417,7 +495,7 @@ class ParameterServer:
                 self._round_count = 0
             return res.accepted
         if res.apply:
-            self.apply(grads, res.weight)
+            self.apply(grads, res.weight, worker_id)
         return res.accepted
 
     _round_count = 0
@@ -557,7 +635,7 @@ class ParameterServer:
         step = self.core.global_step
         path = path or ckpt.path_for(self.cfg.ckpt_dir, step)
         ckpt.save(path, self.layout, self.arena, self.counters, step, self.cfg.mode, self.total_workers, self.lr,
-                  self.momentum_buf, self.cfg.to_json())
+                  self.momentum_buf, self.cfg.to_json(), dc_meansquare=self._dc_ms)
         self.log(f"[Checkpoint] global step {step} -> {path}")
         return path
 
@@ -572,7 +650,7 @@ class ParameterServer:
             if path is None:
                 self.log("[Resume] no checkpoint found; starting fresh")
                 return
-        arena, counters, step, mom, _ = ckpt.restore(path, self.layout)
+        arena, counters, step, mom, obj = ckpt.restore(path, self.layout)
         self.arena.copy_(arena.to(self.device))
         self._wire_stale = True
         self.counters = counters
@@ -580,6 +658,12 @@ class ParameterServer:
         if mom is not None and self.momentum_buf is not None:
             self.momentum_buf.copy_(mom.to(self.device))
             self._mom_first = False
+        # delay compensation: the mean square travels with the checkpoint (absent in older ones: it
+        # stays zero); the backups do not, so every worker is uncompensated until its next fetch
+        self._dc_valid.clear()
+        ms = obj.get("server_optimizer_state", {}).get("dc_meansquare")
+        if ms is not None and self._dc_ms is not None:
+            self._dc_ms.copy_(ms.to(self.device))
         self.log(f"[Resume] restored global step {step} from {path}")
 
     # ------------------------------------------------------------------ metrics
@@ -591,6 +675,10 @@ class ParameterServer:
         m["optimizer"] = self.cfg.optimizer
         if self._lars:
             m["lars_trust_ratio"] = self.lars_trust_ratios()
+        if self._dc:
+            m["delay_compensation"] = {"lambda": float(self.cfg.dc_lambda), "adaptive": bool(self.cfg.dc_adaptive),
+                                       "compensated_pushes": int(self.dc_compensated),
+                                       "uncompensated_pushes": int(self.dc_uncompensated)}
         m["bytes_pushed"] = int(self.bytes_pushed)
         m["bytes_fetched"] = int(self.bytes_fetched)
         if self.images_processed:
@@ -646,7 +734,7 @@ class ParameterServer:
                     got, total = self.register_worker(f"rank{msg.src}", msg.a)
                     mbox.reply(msg.src, CP.Msg(CP.R_REGISTERED, 0, got, total))
                 elif t == CP.FETCH:
-                    gs = self.core.on_fetch(wid)
+                    gs = self.note_fetch(wid)
                     for prev in pending_send.pop(wid, []):
                         prev.wait()
                     pending_send[wid] = [transport.isend(b, rank_of[wid]) for b in snaps[wid].pack(self.arena)]
@@ -679,7 +767,7 @@ class ParameterServer:
                     res = self.core.on_push(wid, ls)
                     self.bytes_pushed += slots[wid].numel() * slots[wid].element_size()
                     if res.apply:
-                        self.apply(slots[wid], res.weight)
+                        self.apply(slots[wid], res.weight, wid)
                         if bwork is not None:
                             self.push_buffers(wid, bufslots[wid])
                         self.maybe_checkpoint()
@@ -699,7 +787,7 @@ class ParameterServer:
                         res = self.core.on_push(wid, ls)
                         self.bytes_pushed += _wire_bytes(grads, n)
                         if res.apply:
-                            self.apply(grads, res.weight)
+                            self.apply(grads, res.weight, wid)
                             if box.get("bufs") is not None:
                                 self.push_buffers(wid, box["bufs"])
                             self.maybe_checkpoint()

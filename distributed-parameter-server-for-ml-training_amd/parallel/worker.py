@@ -253,9 +253,7 @@ class LocalAsyncChannel:
         return self.server.register_worker(name, requested_id)
 
     def fetch(self, worker_id, local_arena):
-        gs = self.server.core.on_fetch(worker_id)
-        local_arena.copy_(self.server.arena)
-        return gs
+        return self.server.note_fetch(worker_id, dst=local_arena)
 
     def push(self, worker_id, grads, local_step, buffers=None):
         ev, box = threading.Event(), {"bufs": buffers}

@@ -7,7 +7,9 @@ de-facto wire layout is the FetchReply payload ``{state_dict_name: ndarray}``
     {"format": "psx-ckpt-v1",
      "parameters": OrderedDict{name: tensor}   # keys/order/shapes/dtypes = reference state_dict
      "global_step": int, "mode": str, "total_workers": int, "lr": float,
-     "server_optimizer_state": {"momentum": tensor | None}, "config": json str}
+     "server_optimizer_state": {"momentum": tensor | None,
+                                "dc_meansquare": tensor   # optional: --dc-adaptive mean square
+                                }, "config": json str}
 
 Written with torch.save to a temp file + atomic rename; loaded with
 ``torch.load(weights_only=True)`` (no arbitrary unpickling). ``parameters`` can be fed straight
@@ -24,7 +26,8 @@ FORMAT = "psx-ckpt-v1"
 
 
 def save(path: str, layout, arena: torch.Tensor, counters: torch.Tensor | None, global_step: int, mode: str,
-         total_workers: int, lr: float, momentum_buf: torch.Tensor | None = None, config_json: str = "") -> str:
+         total_workers: int, lr: float, momentum_buf: torch.Tensor | None = None, config_json: str = "",
+         dc_meansquare: torch.Tensor | None = None) -> str:
     sd = layout.to_state_dict(arena, counters)
     obj = {
         "format": FORMAT,
@@ -36,6 +39,8 @@ def save(path: str, layout, arena: torch.Tensor, counters: torch.Tensor | None, 
         "server_optimizer_state": {"momentum": None if momentum_buf is None else momentum_buf.detach().cpu()},
         "config": config_json,
     }
+    if dc_meansquare is not None:  # optional key: checkpoints without it load, ms starts at zero
+        obj["server_optimizer_state"]["dc_meansquare"] = dc_meansquare.detach().cpu()
     d = os.path.dirname(os.path.abspath(path))
     os.makedirs(d, exist_ok=True)
     tmp = path + ".tmp"

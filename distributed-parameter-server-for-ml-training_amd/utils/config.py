@@ -11,7 +11,8 @@ Keeps every flag and environment variable of the reference with the same default
 
 and adds the MI355X-native knobs: --gpus/--nproc, --codec, --topk-ratio,
 --dtype, --momentum/--weight-decay (server optimizer, default 0 = reference parity),
---optimizer {sgd,lars} with --lars-trust/--lars-eps, --model,
+--optimizer {sgd,lars} with --lars-trust/--lars-eps, --dc-lambda/--dc-adaptive (async delay
+compensation), --model,
 --synthetic, --ckpt-every/--resume, --sync-semantics {barrier,reference}, --topology.
 Precedence: explicit CLI flag > JSON config file (--config) > environment > default.
 """
@@ -65,6 +66,14 @@ class PSConfig:
     optimizer: str = "sgd"
     lars_trust: float = 0.001
     lars_eps: float = 1e-8
+    # async delay compensation (DC-ASGD, csrc/kernels/dcasgd.hip): the server keeps the parameters
+    # each worker last fetched (bak) and applies g + lam * g * g * (w - bak) in place of g.
+    # dc_lambda 0 = off; dc_adaptive: lam = dc_lambda / sqrt(ms + dc_eps) with ms the running mean
+    # square of the gradients (decay dc_decay). Async mode, SGD server, unsharded.
+    dc_lambda: float = 0.0
+    dc_adaptive: bool = False
+    dc_decay: float = 0.95
+    dc_eps: float = 1e-7
     sync_semantics: str = "barrier"  # barrier (wait-for-N) | reference (count-triggered)
     # The reference server never updates BN running statistics and every fetch overwrites the
     # workers' copies (server.py:96,131-133 + worker.py:252), so evaluation runs on near-initial
@@ -132,6 +141,17 @@ class PSConfig:
                 raise ValueError("--optimizer lars needs whole tensors on one server: not with --topology sharded")
             if self.overlap is True:  # a gradient bucket may split a tensor
                 raise ValueError("--optimizer lars updates the whole arena at once: not with --overlap")
+        if self.dc_lambda < 0.0:
+            raise ValueError("--dc-lambda must be >= 0")
+        if self.dc_adaptive and not self.dc_lambda > 0.0:
+            raise ValueError("--dc-adaptive scales --dc-lambda: give --dc-lambda > 0")
+        if not (0.0 <= self.dc_decay < 1.0):
+            raise ValueError("--dc-decay must be in [0, 1)")
+        if self.dc_lambda > 0.0:
+            if self.mode != "async":  # every sync push has staleness 0: nothing to compensate
+                raise ValueError("--dc-lambda compensates gradient staleness: --mode async only")
+            if self.optimizer == "lars":
+                raise ValueError("--dc-lambda runs on the SGD server update: not with --optimizer lars")
         if self.topology == "sharded":  # parallel/sharded.py scope
             if self.mode != "sync" or self.codec not in ("fp16", "none") or self.bn_sync or self.ckpt_every \
                     or self.resume or max(1, self.sync_steps) != 1 or self.overlap is True:
@@ -216,6 +236,12 @@ def add_arguments(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
            "uses --momentum / --weight-decay; Python server, whole-arena updates)")
     A("--lars-trust", type=float, default=None, help="LARS trust coefficient (default 0.001)")
     A("--lars-eps", type=float, default=None, help="LARS denominator epsilon (default 1e-8)")
+    A("--dc-lambda", type=float, default=None,
+      help="async delay compensation (DC-ASGD): apply g + lambda*g*g*(w - w_at_fetch); 0 = off (default)")
+    A("--dc-adaptive", action="store_true", default=None,
+      help="with --dc-lambda: lambda / sqrt(running mean square of g + --dc-eps)")
+    A("--dc-decay", type=float, default=None, help="--dc-adaptive: decay of the mean square (default 0.95)")
+    A("--dc-eps", type=float, default=None, help="--dc-adaptive: epsilon under the square root (default 1e-7)")
     A("--sync-semantics", choices=["barrier", "reference"], default=None)
     A("--bn-sync", action="store_true", default=None, help="workers push BN running stats; server averages")
     A("--deterministic", dest="deterministic", action="store_true", default=None,
