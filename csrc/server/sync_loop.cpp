@@ -61,6 +61,8 @@ struct SyncRt {
   int (*sgd_apply_multi)(float*, const void* const*, int, float*, long, float, float, float, float, int, int, void*,
                          hipStream_t);
   int (*gather_f32)(const float*, const long*, long, float*, hipStream_t);
+  int (*guard_apply_multi)(float*, const void* const*, int, int, float*, float*, long, double*, void*, float, float,
+                           float, float, float, int, void*, hipStream_t);
 };
 
 template <typename F>
@@ -124,6 +126,14 @@ struct PsxSyncCfg {  // mirrored by parallel/native_sync.py (ctypes.Structure)
   // round's apply) — the state a shrunk job resumes from without a checkpoint rollback
   float* snap;
   float* snap_mom;  // momentum buffer snapshots (3 x n_params; nullable)
+  // --clip-norm / --skip-nonfinite (csrc/kernels/gguard.hip; serial round only): the whole-arena
+  // update goes through psx_guard_apply_multi. The guard has no parameter state, so the snapshots
+  // need nothing more; its counters in guard_state are not rolled back by a shrink.
+  float clip_norm;
+  int guard_on;
+  float* stage;       // fp32 [n_params]: the round's gradient sum
+  double* partials;   // [ceil(n_params / psx_guard_chunk())]
+  void* guard_state;  // psx_guard_state_bytes()
 };
 
 // one round in flight: its completion event and the timing events around its apply ranges
@@ -272,11 +282,16 @@ void apply_range(PsxSync* S, long lo, long hi, void* img, hipStream_t st) {
   // the kernel wrappers report hipGetLastError(): clear a hipErrorNotReady of an earlier
   // hipEventQuery (retire) from this thread's error slot
   (void)hipGetLastError();
-  if (S->rt.sgd_apply_multi(S->c.arena + lo, srcs.data(), S->c.nworkers, S->c.mom_buf ? S->c.mom_buf + lo : nullptr,
-                            hi - lo, S->c.lr, 1.f / (float)S->c.nworkers, S->c.momentum, S->c.weight_decay,
-                            S->c.mom_first, S->c.grad_fp16, img, st) &&
-      !S->err)
-    S->err = -61;
+  const float gscale = 1.f / (float)S->c.nworkers;
+  const int rc =
+      S->c.guard_on  // whole arena only (psx_sync_create refuses the guard with buckets)
+          ? S->rt.guard_apply_multi(S->c.arena, srcs.data(), S->c.nworkers, S->c.grad_fp16, S->c.stage, S->c.mom_buf,
+                                    hi - lo, S->c.partials, S->c.guard_state, S->c.lr, gscale, S->c.momentum,
+                                    S->c.weight_decay, S->c.clip_norm, S->c.mom_first, img, st)
+          : S->rt.sgd_apply_multi(S->c.arena + lo, srcs.data(), S->c.nworkers,
+                                  S->c.mom_buf ? S->c.mom_buf + lo : nullptr, hi - lo, S->c.lr, gscale, S->c.momentum,
+                                  S->c.weight_decay, S->c.mom_first, S->c.grad_fp16, img, st);
+  if (rc && !S->err) S->err = -61;
   if (timed) PSX_SHIP(S, hipEventRecord(sl.t1[sl.nt++], st));
 }
 
@@ -396,7 +411,8 @@ void* psx_sync_create(const PsxSyncCfg* cfg, const char* runtime_path, const cha
     return nullptr;
   }
   if (cfg->nworkers < 1 || cfg->nworkers > 32 || !cfg->comm ||
-      (cfg->nbuckets > 0 && (!cfg->buckets || !cfg->comm_stream || !cfg->full_wire))) {
+      (cfg->nbuckets > 0 && (!cfg->buckets || !cfg->comm_stream || !cfg->full_wire)) ||
+      (cfg->guard_on && (cfg->nbuckets > 0 || !cfg->stage || !cfg->partials || !cfg->guard_state))) {
     fprintf(stderr, "psx_sync_create: invalid configuration\n");
     return nullptr;
   }
@@ -408,7 +424,8 @@ void* psx_sync_create(const PsxSyncCfg* cfg, const char* runtime_path, const cha
                   bindf(rt, "psx_ps_on_applied", &r.ps_on_applied) &&
                   bindf(rt, "psx_ps_record_update_time", &r.ps_record_update_time) &&
                   bindf(rt, "psx_ps_global_step", &r.ps_global_step) &&
-                  bindf(kn, "psx_sgd_apply_multi", &r.sgd_apply_multi) && bindf(kn, "psx_gather_f32", &r.gather_f32);
+                  bindf(kn, "psx_sgd_apply_multi", &r.sgd_apply_multi) && bindf(kn, "psx_gather_f32", &r.gather_f32) &&
+                  bindf(kn, "psx_guard_apply_multi", &r.guard_apply_multi);
   if (!ok) {
     delete S;
     return nullptr;

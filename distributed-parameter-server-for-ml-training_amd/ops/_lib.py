@@ -109,6 +109,10 @@ _KERNEL_SIGS = {
     "psx_lars_apply": (i32, [vp, vp, vp, i64, vp, i32, i32, vp, vp, f32, f32, f32, f32, f32, f32, i32, vp, vp]),
     "psx_dc_apply": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, i32, i32, vp, vp]),
     "psx_dc_fetch_copy": (i32, [vp, vp, vp, i64, i64, vp]),
+    "psx_guard_chunk": (i32, []),
+    "psx_guard_state_bytes": (i32, []),
+    "psx_guard_apply_multi": (i32, [vp, vp, i32, i32, vp, vp, i64, vp, vp, f32, f32, f32, f32, f32, i32, vp, vp]),
+    "psx_guard_apply": (i32, [vp, vp, vp, i64, vp, vp, f32, f32, f32, f32, f32, i32, vp, vp]),
 }
 
 _RUNTIME_SIGS = {

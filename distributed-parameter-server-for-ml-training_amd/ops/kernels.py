@@ -738,6 +738,88 @@ def dc_fetch_copy(src, dst, bak, n_params=None):
     check(kernels().psx_dc_fetch_copy(ptr(src), ptr(dst), ptr(bak), n_arena, n_params, stream_ptr()), "dc_fetch_copy")
 
 
+GUARD_CHUNK = 8192  # kGuardChunk in csrc/kernels/gguard.hip: elements per workgroup of the guard grid
+_GUARD_STATE = [("S", "<f8"), ("norm", "<f8"), ("coef", "<f4"), ("skip", "<i4"), ("rounds", "<i8"),
+                ("clipped_rounds", "<i8"), ("skipped_rounds", "<i8"), ("norm_last", "<f8"), ("norm_max", "<f8"),
+                ("norm_sum", "<f8")]  # GuardState
+
+
+class GuardState:
+    """The scratch and the device state block of the gradient guard (csrc/kernels/gguard.hip) for
+    an update of ``n`` elements: one double partial of sum s^2 per workgroup, and GuardState: the
+    last round's {S, norm, coef, skip} and the running counters (rounds, clipped_rounds,
+    skipped_rounds, norm_last, norm_max, norm_sum; the last two over finite rounds only)."""
+
+    def __init__(self, n, device):
+        import numpy as np
+
+        self.n = int(n)
+        assert self.n > 0, "GuardState n"
+        self.nblocks = -(-self.n // GUARD_CHUNK)
+        self._dtype = np.dtype(_GUARD_STATE)
+        dev = torch.device(device)
+        if dev.type == "cuda":
+            assert kernels().psx_guard_state_bytes() == self._dtype.itemsize, "GuardState layout"
+            assert kernels().psx_guard_chunk() == GUARD_CHUNK, "kGuardChunk"
+        self.partials = torch.zeros(self.nblocks, dtype=torch.float64, device=dev)
+        self.state = torch.zeros(self._dtype.itemsize, dtype=torch.uint8, device=dev)
+        self.device = self.state.device  # with the device index filled in
+
+    def read(self) -> dict:
+        """The state block read back (synchronises: for metrics and tests, not per round)."""
+        r = self.state.cpu().numpy().view(self._dtype)[0]
+        out = {k: (float(r[k]) if self._dtype[k].kind == "f" else int(r[k])) for k in self._dtype.names}
+        out["skip"] = bool(out["skip"])
+        return out
+
+
+def _guard_common(p, stage, state, buf, img, n, clip_norm, what):
+    n = state.n if n is None else n
+    assert n == state.n and p.dtype == torch.float32 and p.is_contiguous() and p.numel() >= n, f"{what} p"
+    assert p.device == state.device and p.device.type == "cuda", f"{what} device"
+    assert stage.dtype == torch.float32 and stage.is_contiguous() and stage.numel() >= n and stage.device == p.device, \
+        f"{what} stage"
+    if buf is not None:
+        assert buf.dtype == torch.float32 and buf.is_contiguous() and buf.numel() >= n and buf.device == p.device, \
+            f"{what} buf"
+    if img is not None:
+        assert img.dtype == torch.bfloat16 and img.is_contiguous() and img.numel() >= n and img.device == p.device, \
+            f"{what} img"
+    assert clip_norm >= 0.0, f"{what} clip_norm"
+    return n
+
+
+def guard_apply_multi(p, srcs, stage, state: GuardState, lr, gscale=1.0, momentum=0.0, wd=0.0, clip_norm=0.0,
+                      buf=None, first=False, n=None, img=None):
+    """The guarded server update from the W gathered wires (csrc/kernels/gguard.hip): ``stage``
+    receives s = sum_k srcs[k] (fp32, list order, as sgd_apply_multi forms it); norm = gscale * |s|;
+    a non-finite sum of squares skips the round (p, buf, img untouched); otherwise the update of
+    sgd_apply_multi with gscale * coef, coef = min(1, clip_norm / (norm + 1e-6)) (1 with clip_norm
+    0). All sources fp16 or all fp32; at most 32. Three launches on the current stream, no host
+    synchronisation; the decision and the counters are in ``state``."""
+    n = _guard_common(p, stage, state, buf, img, n, clip_norm, "guard_apply_multi")
+    assert 1 <= len(srcs) <= 32
+    fp16 = srcs[0].dtype == torch.float16
+    assert srcs[0].dtype in (torch.float16, torch.float32), "guard_apply_multi"
+    assert all(s.dtype == srcs[0].dtype and s.numel() >= n and s.device == p.device and s.is_contiguous()
+               and s.data_ptr() != stage.data_ptr() for s in srcs), "guard_apply_multi"
+    arr = (C.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
+    check(kernels().psx_guard_apply_multi(ptr(p), arr, len(srcs), int(fp16), ptr(stage), ptr(buf), n,
+                                          ptr(state.partials), ptr(state.state), float(lr), float(gscale),
+                                          float(momentum), float(wd), float(clip_norm), int(first), ptr(img),
+                                          stream_ptr()), "guard_apply_multi")
+
+
+def guard_apply(p, stage, state: GuardState, lr, gscale=1.0, momentum=0.0, wd=0.0, clip_norm=0.0, buf=None,
+                first=False, n=None, img=None):
+    """guard_apply_multi for a gradient sum that is already dense fp32 in ``stage`` (decoded q8 /
+    top-k payloads, an accumulated round): norms only, no rewrite, then the same decision and apply."""
+    n = _guard_common(p, stage, state, buf, img, n, clip_norm, "guard_apply")
+    check(kernels().psx_guard_apply(ptr(p), ptr(stage), ptr(buf), n, ptr(state.partials), ptr(state.state),
+                                    float(lr), float(gscale), float(momentum), float(wd), float(clip_norm),
+                                    int(first), ptr(img), stream_ptr()), "guard_apply")
+
+
 def grad_aggregate(srcs_dev_ptrs, nsrc, src_fp16, dst, n, scale=1.0, accumulate=False):
     """srcs_dev_ptrs: int64 device tensor holding nsrc device pointers."""
     check(kernels().psx_grad_aggregate(ptr(srcs_dev_ptrs), nsrc, int(src_fp16), ptr(dst),

@@ -13,7 +13,9 @@ the rounds' device completion through ``psx_sync_progress``.
 
 Scope (otherwise the Python channel runs the server side, PSX_NATIVE_SYNC=0 forces it): sync
 mode, dedicated topology on the native transport, dense fp16 / fp32 gradient wire, fetch payload
-fp32 or bf16conv (WeightWire / BucketWire), no --bn-sync.
+fp32 or bf16conv (WeightWire / BucketWire), no --bn-sync. The gradient guard (--clip-norm /
+--skip-nonfinite) is served by the serial round: it launches ``psx_guard_apply_multi`` on the
+server's staging buffer and device state block, so the counters are the Python server's own.
 """
 from __future__ import annotations
 
@@ -43,7 +45,8 @@ class SyncCfg(C.Structure):
                 ("wire_buf", vp), ("wire_bytes", i64), ("wire_img", vp), ("small_idx", vp), ("small_n", i64),
                 ("wire_small", vp), ("nbuckets", i32), ("buckets", vp), ("full_wire", vp), ("full_wire_bytes", i64),
                 ("primed", i32), ("upd_stream", vp), ("comm_stream", vp), ("ckpt_every", C.c_longlong),
-                ("ckpt_cb", CKPT_CB), ("snap", vp), ("snap_mom", vp)]
+                ("ckpt_cb", CKPT_CB), ("snap", vp), ("snap_mom", vp), ("clip_norm", f32), ("guard_on", i32),
+                ("stage", vp), ("partials", vp), ("guard_state", vp)]
 
 
 _SIGS = {
@@ -152,6 +155,12 @@ class NativeSyncServer:
             if cfg.momentum and server.momentum_buf is not None:
                 self.snap_mom = torch.empty(3 * server.n, dtype=torch.float32, device=dev)
                 c.snap_mom = self.snap_mom.data_ptr()
+        if server._guard:  # csrc/kernels/gguard.hip in place of psx_sgd_apply_multi (serial round only)
+            if overlap:
+                raise ValueError("--clip-norm / --skip-nonfinite update the whole arena at once: no bucketed rounds")
+            gst = server._guard_state
+            c.clip_norm, c.guard_on = float(cfg.clip_norm), 1
+            c.stage, c.partials, c.guard_state = server.agg.data_ptr(), gst.partials.data_ptr(), gst.state.data_ptr()
         if overlap:
             wire = chan.wire
             bks = []

@@ -145,6 +145,9 @@ def run_local_threads(cfg, steps: int, log=print, emit: bool = True) -> dict:
     if cfg.optimizer == "lars":
         raise ValueError("run_local_threads is bound to the native event loop, which applies plain SGD: "
                          "--optimizer lars is not available here")
+    if cfg.grad_guard:
+        raise ValueError("run_local_threads is bound to the native event loop, which applies plain SGD: "
+                         "--clip-norm / --skip-nonfinite are not available here")
     cfg.resolve_overlap(1)
     device = _device_for(0)
     W = cfg.workers

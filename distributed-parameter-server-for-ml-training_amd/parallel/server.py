@@ -76,6 +76,22 @@ class ParameterServer:
                 from ..ops import kernels as K
 
                 self._lars_tab = K.lars_table(layout, self.device)
+        # --clip-norm / --skip-nonfinite: every whole-arena update goes through _guard_update (the
+        # three launches of csrc/kernels/gguard.hip, staged through agg); no parameter state, only
+        # the counters: in the device state block, or in _guard_host on a CPU arena
+        self._guard = cfg.grad_guard
+        self._guard_state = None   # device scratch + state block (ops/kernels.py GuardState)
+        self._guard_host = None
+        self._guard_skip_logged = False
+        if self._guard:
+            self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+            if self.device.type == "cuda":
+                from ..ops import kernels as K
+
+                self._guard_state = K.GuardState(self.n, self.device)
+            else:
+                self._guard_host = {"rounds": 0, "clipped_rounds": 0, "skipped_rounds": 0, "norm_last": 0.0,
+                                    "norm_max": 0.0, "norm_sum": 0.0}
         # --dc-lambda (async): delay compensation (csrc/kernels/dcasgd.hip). Every fetch leaves the
         # worker's backup of the fp32 parameters (note_fetch); the apply of a push from a worker
         # with a valid backup is g + lam * g * g * (w - bak) in place of g (_apply_dc).
@@ -111,7 +127,7 @@ class ParameterServer:
             self._apply_dc(grads, weight, worker_id)
             return self.finish_round_apply(self._time_end(t0))
         if grads.dtype == torch.int32:  # top-k payload (parallel/topk.py)
-            if not self.cfg.momentum and not self.cfg.weight_decay and not self._lars:
+            if not self.cfg.momentum and not self.cfg.weight_decay and not self._lars and not self._guard:
                 # no optimizer state: scatter straight into the fp32 master parameters
                 topk.decode_add(grads, self.params, -self.lr * weight, self._kcap)
                 self._wire_stale = True  # the bf16 image was not written by this update
@@ -127,8 +143,9 @@ class ParameterServer:
         """The update from q8 payloads, decoded and summed in fp32 in list order: one fused
         launch on the device (the weight image, when enabled, written in the same pass); the
         torch decode into the aggregation buffer on a CPU arena. LARS: decoded into the
-        aggregation buffer on either, then the dense entry of the LARS pair."""
-        if self.device.type == "cuda" and not self._lars:
+        aggregation buffer on either, then the dense entry of the LARS pair; the gradient guard
+        likewise (its dense entry)."""
+        if self.device.type == "cuda" and not self._lars and not self._guard:
             from ..ops import kernels as K
 
             img = self.wire.img[: self.n] if self.wire is not None else None
@@ -268,6 +285,13 @@ class ParameterServer:
         if self._lars:
             self._lars_whole(lo, hi)
             return self._lars_update([g], weight)
+        if self._guard:
+            self._guard_whole(lo, hi)
+            return self._guard_update([g], weight)
+        self._sgd_range(g, weight, lo, hi)
+
+    def _sgd_range(self, g: torch.Tensor, weight: float, lo: int, hi: int):
+        """apply_range's plain SGD form (no LARS, no guard routing)."""
         p = self.params[lo:hi]
         buf = self.momentum_buf[lo:hi] if self.momentum_buf is not None else None
         if self.device.type == "cuda":
@@ -296,6 +320,9 @@ class ParameterServer:
         if self._lars:
             self._lars_whole(lo, hi)
             return self._lars_update(list(srcs), weight)
+        if self._guard:
+            self._guard_whole(lo, hi)
+            return self._guard_update(list(srcs), weight)
         if self.device.type == "cuda":
             from ..ops import kernels as K
 
@@ -379,6 +406,78 @@ class ParameterServer:
         if not r.numel():
             return None
         return {"min": float(r.min()), "median": float(r.median()), "max": float(r.max())}
+
+    # ------------------------------------------------------------------ gradient guard (--clip-norm, --skip-nonfinite)
+    def _guard_whole(self, lo: int, hi: int):
+        if (lo, hi) != (0, self.n):
+            raise ValueError(f"--clip-norm / --skip-nonfinite need the whole gradient's norm before the first parameter "
+                             f"moves: a partial range [{lo}, {hi}) of {self.n} cannot be applied (no bucketed or "
+                             f"sharded updates)")
+
+    def _guard_update(self, srcs: list, weight: float):
+        """The whole-arena guarded update from dense wires (fp16 / fp32, summed in fp32 in list
+        order) or from the aggregation buffer itself (a decoded or accumulated sum):
+        S = sum s^2, norm = weight * sqrt(S); S not finite: the round is skipped (parameters,
+        momentum buffer and fetch image untouched; it still counts as a round, and consumes the
+        momentum 'first step' flag: the buffer starts as zeros, so momentum * 0 + d of the next
+        round has the value the first-step form would have given); else coef = min(1, clip_norm /
+        (norm + 1e-6)) (1 without --clip-norm), rounded to fp32, and apply_range's update with
+        weight * coef (one fp32 multiply): weight decay is added after the scaling, not clipped.
+        Device: the three launches of csrc/kernels/gguard.hip, no host synchronisation; CPU arena:
+        the same formula in torch (equal to a tolerance, not bit for bit: the reduction orders
+        differ)."""
+        cfg = self.cfg
+        staged = len(srcs) == 1 and srcs[0].dtype == torch.float32 and srcs[0].data_ptr() == self.agg.data_ptr()
+        if self.device.type == "cuda":
+            from ..ops import kernels as K
+
+            kw = dict(lr=self.lr, gscale=weight, momentum=cfg.momentum, wd=cfg.weight_decay, clip_norm=cfg.clip_norm,
+                      buf=self.momentum_buf, first=self._mom_first, n=self.n,
+                      img=self.wire.img[: self.n] if self.wire is not None else None)
+            if staged:
+                K.guard_apply(self.params, self.agg, self._guard_state, **kw)
+            else:
+                K.guard_apply_multi(self.params, [s[: self.n] for s in srcs], self.agg, self._guard_state, **kw)
+            return
+        import math
+
+        import numpy as np
+
+        if not staged:
+            self.agg.zero_()
+            for s in srcs:  # fixed order, fp32 accumulation
+                self.agg.add_(s[: self.n].to(torch.float32))
+        S = float(self.agg.double().square().sum())
+        h = self._guard_host
+        h["rounds"] += 1
+        if not math.isfinite(S):
+            h["skipped_rounds"] += 1
+            h["norm_last"] = float("nan") if S != S else float("inf")
+            return
+        norm = float(np.float32(weight)) * math.sqrt(S)
+        coef = np.float32(min(1.0, cfg.clip_norm / (norm + 1e-6))) if cfg.clip_norm > 0 else np.float32(1.0)
+        h["clipped_rounds"] += int(coef < 1.0)
+        h["norm_last"] = norm
+        h["norm_max"] = max(h["norm_max"], norm)
+        h["norm_sum"] += norm
+        self._sgd_range(self.agg, float(np.float32(weight) * coef), 0, self.n)
+
+    def guard_counters(self):
+        """The guard's running counters (read from the device state block here, not per round);
+        None with the guard off. Not rolled back by an elastic shrink: a round that was applied and
+        then rolled back stays counted."""
+        if not self._guard:
+            return None
+        h = self._guard_state.read() if self._guard_state is not None else self._guard_host
+        if h["skipped_rounds"] and not self._guard_skip_logged:
+            self._guard_skip_logged = True
+            self.log(f"[GradientGuard] {h['skipped_rounds']} of {h['rounds']} updates so far skipped: "
+                     f"non-finite gradient sum")
+        fin = h["rounds"] - h["skipped_rounds"]
+        return {"clip_norm": float(self.cfg.clip_norm), "rounds": int(h["rounds"]),
+                "clipped_rounds": int(h["clipped_rounds"]), "skipped_rounds": int(h["skipped_rounds"]),
+                "norm_last": float(h["norm_last"]), "norm_max": float(h["norm_max"]),
+                "norm_mean": float(h["norm_sum"]) / fin if fin else None}
 
     def finish_round_apply(self, dt: float = -1.0):
         """Closes one update (global_step + 1). ``dt`` >= 0: its host-measured time (CPU arena);
@@ -575,6 +674,8 @@ class ParameterServer:
         t0 = self._time_begin()
         if self._lars:
             self._lars_update(list(srcs), res.weight)
+        elif self._guard:
+            self._guard_update(list(srcs), res.weight)
         elif self.device.type == "cuda":
             from ..ops import kernels as K
 
@@ -675,6 +776,8 @@ class ParameterServer:
         m["optimizer"] = self.cfg.optimizer
         if self._lars:
             m["lars_trust_ratio"] = self.lars_trust_ratios()
+        if self._guard:
+            m["gradient_guard"] = self.guard_counters()
         if self._dc:
             m["delay_compensation"] = {"lambda": float(self.cfg.dc_lambda), "adaptive": bool(self.cfg.dc_adaptive),
                                        "compensated_pushes": int(self.dc_compensated),

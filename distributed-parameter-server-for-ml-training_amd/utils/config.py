@@ -12,7 +12,7 @@ Keeps every flag and environment variable of the reference with the same default
 and adds the MI355X-native knobs: --gpus/--nproc, --codec, --topk-ratio,
 --dtype, --momentum/--weight-decay (server optimizer, default 0 = reference parity),
 --optimizer {sgd,lars} with --lars-trust/--lars-eps, --dc-lambda/--dc-adaptive (async delay
-compensation), --model,
+compensation), --clip-norm/--skip-nonfinite (global-norm clipping, non-finite guard), --model,
 --synthetic, --ckpt-every/--resume, --sync-semantics {barrier,reference}, --topology.
 Precedence: explicit CLI flag > JSON config file (--config) > environment > default.
 """
@@ -74,6 +74,13 @@ class PSConfig:
     dc_adaptive: bool = False
     dc_decay: float = 0.95
     dc_eps: float = 1e-7
+    # gradient guard (csrc/kernels/gguard.hip): clip_norm C > 0 scales a round whose global gradient
+    # norm (of the weighted fp32 sum the server applies) exceeds C by C / (norm + 1e-6), torch's
+    # clip_grad_norm_ form, weight decay not clipped; skip_nonfinite drops a round whose sum holds
+    # inf / NaN instead of poisoning the arena. clip_norm > 0 implies skip_nonfinite. SGD server,
+    # whole-arena updates only: no bucketed overlap, graph round, sharded server, native async loop.
+    clip_norm: float = 0.0
+    skip_nonfinite: bool = False
     sync_semantics: str = "barrier"  # barrier (wait-for-N) | reference (count-triggered)
     # The reference server never updates BN running statistics and every fetch overwrites the
     # workers' copies (server.py:96,131-133 + worker.py:252), so evaluation runs on near-initial
@@ -152,6 +159,21 @@ class PSConfig:
                 raise ValueError("--dc-lambda compensates gradient staleness: --mode async only")
             if self.optimizer == "lars":
                 raise ValueError("--dc-lambda runs on the SGD server update: not with --optimizer lars")
+        if not self.clip_norm >= 0.0:
+            raise ValueError("--clip-norm must be >= 0")
+        if self.clip_norm > 0.0:
+            self.skip_nonfinite = True
+        if self.grad_guard:
+            if self.optimizer == "lars":
+                raise ValueError("--clip-norm / --skip-nonfinite run on the SGD server update: not with --optimizer lars")
+            if self.dc_lambda > 0.0:
+                raise ValueError("--clip-norm / --skip-nonfinite run on the SGD server update: not with --dc-lambda")
+            if self.topology == "sharded":  # no shard sees the whole gradient
+                raise ValueError("--clip-norm / --skip-nonfinite need the whole gradient's norm on one server: "
+                                 "not with --topology sharded")
+            if self.overlap is True:  # a bucket is applied before the others have arrived
+                raise ValueError("--clip-norm / --skip-nonfinite need the whole gradient's norm before the first "
+                                 "parameter moves: not with --overlap")
         if self.topology == "sharded":  # parallel/sharded.py scope
             if self.mode != "sync" or self.codec not in ("fp16", "none") or self.bn_sync or self.ckpt_every \
                     or self.resume or max(1, self.sync_steps) != 1 or self.overlap is True:
@@ -190,11 +212,18 @@ class PSConfig:
         """--overlap / --no-overlap, or auto: bucketed rounds when there are peers to exchange
         with and the round qualifies (sync, one push per batch, dense wire, rank-0 server). The
         error-feedback codecs (q8, topk) encode the whole gradient at once, and --optimizer lars
-        needs every tensor's norm before its first element moves: no bucketed rounds."""
+        and the gradient guard (--clip-norm / --skip-nonfinite) need a norm of the whole gradient
+        before the first element moves: no bucketed rounds."""
         if self.overlap is None:
             self.overlap = (world > 1 and self.mode == "sync" and max(1, self.sync_steps) == 1
-                            and self.dense_wire and self.topology != "sharded" and self.optimizer != "lars")
+                            and self.dense_wire and self.topology != "sharded" and self.optimizer != "lars"
+                            and not self.grad_guard)
         return bool(self.overlap)
+
+    @property
+    def grad_guard(self) -> bool:
+        """The gradient guard is on: --clip-norm > 0 or --skip-nonfinite."""
+        return self.clip_norm > 0.0 or bool(self.skip_nonfinite)
 
     @property
     def dense_wire(self) -> bool:
@@ -242,6 +271,11 @@ def add_arguments(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
       help="with --dc-lambda: lambda / sqrt(running mean square of g + --dc-eps)")
     A("--dc-decay", type=float, default=None, help="--dc-adaptive: decay of the mean square (default 0.95)")
     A("--dc-eps", type=float, default=None, help="--dc-adaptive: epsilon under the square root (default 1e-7)")
+    A("--clip-norm", type=float, default=None,
+      help="clip the global L2 norm of the applied gradient to C (torch clip_grad_norm_ form; weight decay not "
+           "clipped); 0 = off (default); implies --skip-nonfinite")
+    A("--skip-nonfinite", action="store_true", default=None,
+      help="skip a server update whose gradient sum holds inf / NaN (the round still counts)")
     A("--sync-semantics", choices=["barrier", "reference"], default=None)
     A("--bn-sync", action="store_true", default=None, help="workers push BN running stats; server averages")
     A("--deterministic", dest="deterministic", action="store_true", default=None,

@@ -10,9 +10,14 @@ every epoch:
                       staleness exactly W - 1 and the run is reproducible; --staleness-bound is set
                       high enough that nothing is rejected;
 * ``async_dc_const``  the same with --dc-lambda L, one curve per L of --lambdas-const;
-* ``async_dc_adapt``  the same with --dc-lambda L --dc-adaptive, one curve per L of --lambdas-adapt.
+* ``async_dc_adapt``  the same with --dc-lambda L --dc-adaptive, one curve per L of --lambdas-adapt;
+* ``async_guard``     the async run with --skip-nonfinite alone (the update unchanged): it measures
+                      the mean global norm of the applied gradients, ``norm_mean``;
+* ``async_clip``      the async run with --clip-norm C, one curve per fraction f of --clip-fractions,
+                      C = f * norm_mean (does clipping the global norm steady the late epochs?).
 
-Prints one line per curve (per-epoch test accuracy, final accuracy, compensated pushes) and writes
+Prints one line per curve (per-epoch test accuracy, final accuracy, compensated pushes, the
+gradient guard's counters) and writes
 ``<out>/dc_convergence.json``.
 """
 from __future__ import annotations
@@ -43,7 +48,8 @@ def run(args, mode: str, **dc):
     return {"test_acc_per_epoch": w0["all_accuracies_percent"], "final_test_acc": w0["final_test_accuracy_percent"],
             "global_steps": s["global_steps_completed"], "rejected_pushes": s.get("rejected_pushes", 0),
             "average_staleness": s.get("average_gradient_staleness"),
-            "delay_compensation": s.get("delay_compensation"), "seconds": round(time.time() - t0, 1)}
+            "delay_compensation": s.get("delay_compensation"), "gradient_guard": s.get("gradient_guard"),
+            "seconds": round(time.time() - t0, 1)}
 
 
 def main():
@@ -57,6 +63,8 @@ def main():
     ap.add_argument("--test", type=int, default=2000)
     ap.add_argument("--lambdas-const", default="0.04,1.0")
     ap.add_argument("--lambdas-adapt", default="2.0")
+    ap.add_argument("--clip-fractions", default="1,0.25",
+                    help="--clip-norm curves at these fractions of the measured mean norm ('' = none)")
     ap.add_argument("--out", default="runs/dc_convergence")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
@@ -67,14 +75,23 @@ def main():
     print(f"{args.model}, synthetic hard, W = {args.workers}, batch {args.batch}, lr {args.lr:g}, {args.epochs} epochs "
           f"of {args.train} samples, --bn-sync, fp32 engine, fp16 wire; test accuracy % of worker 0 per epoch",
           flush=True)
+    fracs = [float(v) for v in args.clip_fractions.split(",") if v]
+    if fracs:
+        plan.append(("async_guard", "async", dict(skip_nonfinite=True)))
     runs = {}
-    for name, mode, dc in plan:
+    while plan:
+        name, mode, dc = plan.pop(0)
         r = runs[name] = run(args, mode, **dc)
-        comp = r["delay_compensation"]
+        comp, guard = r["delay_compensation"], r["gradient_guard"]
+        if name == "async_guard":  # the clipping bounds come from this run's mean norm
+            plan += [(f"async_clip_{f:g}xmean", "async", dict(clip_norm=f * guard["norm_mean"])) for f in fracs]
         print(f"{name:22s} acc/epoch {r['test_acc_per_epoch']} final {r['final_test_acc']:.2f}%  "
               f"updates {r['global_steps']} rejected {r['rejected_pushes']} mean staleness {r['average_staleness']}"
               + (f" compensated {comp['compensated_pushes']} uncompensated {comp['uncompensated_pushes']}"
-                 if comp else "") + f"  ({r['seconds']} s)", flush=True)
+                 if comp else "")
+              + (f" clip_norm {guard['clip_norm']:.4g} clipped {guard['clipped_rounds']} skipped "
+                 f"{guard['skipped_rounds']} norm mean {guard['norm_mean']:.4g} max {guard['norm_max']:.4g}"
+                 if guard else "") + f"  ({r['seconds']} s)", flush=True)
     with open(os.path.join(args.out, "dc_convergence.json"), "w") as f:
         json.dump({"config": vars(args), "runs": runs}, f)
 
