@@ -37,8 +37,9 @@ def report(name: str, us: float, nbytes: float, copy_tbs: float):
           flush=True)
 
 
-def step_time(optimizer: str, steps: int, warmup: int, batch: int = 128) -> float:
-    """ms per step of a W = 1 sync loopback (fetch + step + push + server update)."""
+def step_time(optimizer: str, steps: int, warmup: int, batch: int = 128, **hparams) -> float:
+    """ms per step of a W = 1 sync loopback (fetch + step + push + server update). ``hparams``
+    override the server's lr / momentum / weight_decay (bench/adamw_bench.py)."""
     from psx.parallel.compute import make_compute
     from psx.parallel.runner import _wire_dtype, build_state, make_local_channel
     from psx.parallel.server import ParameterServer
@@ -47,9 +48,10 @@ def step_time(optimizer: str, steps: int, warmup: int, batch: int = 128) -> floa
     from psx.utils.data import DeviceDataset
 
     dev = torch.device("cuda", 0)
-    cfg = PSConfig(model="resnet18", mode="sync", workers=1, lr=0.05, batch_size=batch, epochs=10 ** 6,
-                   train_samples=10000, eval_every=0, verbose=0, momentum=0.9, weight_decay=5e-4,
-                   optimizer=optimizer).validate()
+    hp = dict(lr=0.05, momentum=0.9, weight_decay=5e-4)
+    hp.update(hparams)
+    cfg = PSConfig(model="resnet18", mode="sync", workers=1, batch_size=batch, epochs=10 ** 6,
+                   train_samples=10000, eval_every=0, verbose=0, optimizer=optimizer, **hp).validate()
     quiet = lambda *a, **k: None  # noqa: E731
     model, lay, arena, counters = build_state(cfg)
     srv = ParameterServer(cfg, lay, arena.clone(), counters, device=dev, total_workers=1, log=quiet)

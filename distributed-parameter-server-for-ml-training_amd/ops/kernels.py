@@ -699,6 +699,70 @@ def lars_apply(p, stage, table: LarsTable, lr, gscale=1.0, momentum=0.0, wd=0.0,
           "lars_apply")
 
 
+ADAMW_SCALARS = ("step_size", "beta1", "omb1", "beta2", "omb2", "rsqrt_bc2", "eps", "decay")
+
+
+def adamw_scalars(lr, t, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0):
+    """The eight fp32 scalars of AdamW update number ``t`` >= 1, in ADAMW_SCALARS order, as the
+    kernel entry computes them (csrc/kernels/adamw.hip: each in double, rounded to fp32 once):
+    step_size = lr / (1 - beta1^t), beta1, 1 - beta1, beta2, 1 - beta2, rsqrt_bc2 = 1 / sqrt(1 -
+    beta2^t), eps, decay = 1 - lr * wd. Returned as Python floats holding fp32 values."""
+    out = (C.c_float * 8)()
+    check(kernels().psx_adamw_scalars(float(lr), float(beta1), float(beta2), float(eps), float(wd), int(t), out),
+          "adamw_scalars")
+    return [float(x) for x in out]
+
+
+def adamw_scalars_host(lr, t, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0):
+    """adamw_scalars without the kernel library: the same expressions in Python doubles, each
+    rounded with np.float32."""
+    import math
+
+    import numpy as np
+
+    assert t >= 1, "adamw_scalars_host t"
+    vals = (lr / (1.0 - beta1 ** t), beta1, 1.0 - beta1, beta2, 1.0 - beta2, 1.0 / math.sqrt(1.0 - beta2 ** t), eps,
+            1.0 - lr * wd)
+    return [float(np.float32(x)) for x in vals]
+
+
+def adamw_apply_multi(p, srcs, m, v, lr, t, gscale=1.0, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0, n=None, img=None):
+    """The AdamW server update of n contiguous elements from the W gathered wires, update number
+    ``t`` >= 1 (csrc/kernels/adamw.hip), one pass: s = sum_k srcs[k] (fp32, list order, as
+    sgd_apply_multi forms it), g = gscale * s, m = beta1*m + (1-beta1)*g, v = beta2*v +
+    (1-beta2)*g*g, p = p*(1 - lr*wd) - lr/(1-beta1^t) * m / (sqrt(v)/sqrt(1-beta2^t) + eps);
+    ``img`` (bf16) also receives the image of the updated parameters. All sources fp16 or all
+    fp32, at most 32; p, m, v, img and the sources may be slices at any element offset. One launch
+    on the current stream, no host synchronisation."""
+    n = p.numel() if n is None else n
+    dev = p.device
+    assert n > 0 and dev.type == "cuda", "adamw_apply_multi device"
+    assert int(t) >= 1, "adamw_apply_multi t"
+    for x, what in ((p, "p"), (m, "m"), (v, "v")):
+        assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= n and x.device == dev, \
+            f"adamw_apply_multi {what}"
+    assert 1 <= len(srcs) <= 32, "adamw_apply_multi sources"
+    assert srcs[0].dtype in (torch.float16, torch.float32), "adamw_apply_multi"
+    fp16 = srcs[0].dtype == torch.float16
+    state = {p.data_ptr(), m.data_ptr(), v.data_ptr()}
+    assert len(state) == 3, "adamw_apply_multi: p, m, v alias"
+    assert all(s.dtype == srcs[0].dtype and s.numel() >= n and s.device == dev and s.is_contiguous()
+               and s.data_ptr() not in state for s in srcs), "adamw_apply_multi"
+    if img is not None:
+        assert img.dtype == torch.bfloat16 and img.is_contiguous() and img.numel() >= n and img.device == dev, \
+            "adamw_apply_multi img"
+    arr = (C.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
+    check(kernels().psx_adamw_apply_multi(ptr(p), arr, len(srcs), int(fp16), ptr(m), ptr(v), n, float(lr),
+                                          float(gscale), float(beta1), float(beta2), float(eps), float(wd), int(t),
+                                          ptr(img), stream_ptr()), "adamw_apply_multi")
+
+
+def adamw_apply(p, g, m, v, lr, t, gscale=1.0, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0, n=None, img=None):
+    """adamw_apply_multi with one source: a wire, or a gradient sum that is already dense fp32
+    (decoded q8 / top-k payloads, an accumulated round)."""
+    adamw_apply_multi(p, [g], m, v, lr, t, gscale=gscale, beta1=beta1, beta2=beta2, eps=eps, wd=wd, n=n, img=img)
+
+
 def _dc_f32(t, n, dev, what):
     assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n and t.device == dev, what
 

@@ -51,8 +51,10 @@ def graph_round_enabled(cfg, transport) -> bool:
     # exposed xGMI time of the serial round (reduce 22.4 MB + broadcast 22.5 MB) exceeds that
     return (os.environ.get("PSX_GRAPH_ROUND", "0") == "1" and getattr(transport, "native", False)
             and cfg.topology == "colocated" and not cfg.momentum and not cfg.bn_sync
-            and cfg.optimizer != "lars"  # per-bucket applies: a bucket may split a tensor
-            and not cfg.grad_guard)  # ... and none sees the whole gradient's norm
+            # per-bucket applies: a bucket may split a tensor (lars); a captured apply would bake the
+            # update number's scalars into the graph (adamw)
+            and cfg.optimizer == "sgd"
+            and not cfg.grad_guard)  # ... and no bucket sees the whole gradient's norm
 
 
 class GraphRoundChannel(SyncCollectiveChannel):

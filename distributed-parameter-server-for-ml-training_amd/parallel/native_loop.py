@@ -77,10 +77,10 @@ def _lib():
 
 def native_loop_enabled(cfg, transport) -> bool:
     """Default for async jobs on the native transport (PSX_NATIVE_LOOP=0: the Python loop). The
-    C++ loop launches the SGD kernels itself: --optimizer lars and the gradient guard (--clip-norm /
-    --skip-nonfinite) are served by the Python loop."""
+    C++ loop launches the SGD kernels itself: --optimizer lars / adamw and the gradient guard
+    (--clip-norm / --skip-nonfinite) are served by the Python loop."""
     return (os.environ.get("PSX_NATIVE_LOOP", "1") == "1" and getattr(transport, "native", False)
-            and cfg.codec in ("fp16", "none") and not cfg.bn_sync and cfg.optimizer != "lars"
+            and cfg.codec in ("fp16", "none") and not cfg.bn_sync and cfg.optimizer == "sgd"
             and not cfg.grad_guard)
 
 
@@ -97,8 +97,9 @@ class NativeServerLoop:
         self.rank_of_wid = dict(rank_of_wid)
         lay = server.layout
         cfg = server.cfg
-        if cfg.optimizer == "lars":  # csrc/server/event_loop.cpp launches psx_sgd_apply itself
-            raise ValueError("the native event loop applies plain SGD: --optimizer lars runs on the Python server loop")
+        if cfg.optimizer != "sgd":  # csrc/server/event_loop.cpp launches psx_sgd_apply itself
+            raise ValueError(f"the native event loop applies plain SGD: --optimizer {cfg.optimizer} runs on the Python "
+                             f"server loop")
         if cfg.grad_guard:
             raise ValueError("the native event loop applies plain SGD: --clip-norm / --skip-nonfinite run on the "
                              "Python server loop")

@@ -106,7 +106,7 @@ def native_sync_enabled(cfg, transport, chan, server, rank: int) -> bool:
     if not (os.environ.get("PSX_NATIVE_SYNC", "1") == "1" and rank == 0 and server is not None
             and getattr(transport, "native", False) and getattr(transport, "world_size", 1) > 1
             and cfg.mode == "sync" and cfg.topology == "dedicated" and cfg.codec in ("fp16", "none")
-            and cfg.optimizer != "lars"  # the C++ rounds launch the SGD kernels: LARS stays in Python
+            and cfg.optimizer == "sgd"  # the C++ rounds launch the SGD kernels: LARS / AdamW stay in Python
             and not cfg.bn_sync and type(chan) in (SyncCollectiveChannel, OverlapSyncChannel)
             and not getattr(chan, "root_worker", True) and getattr(chan, "agg_mode", "gather") == "gather"):
         return False
@@ -124,8 +124,9 @@ class NativeSyncServer:
 
     def __init__(self, server, transport, chan, elastic: bool = False):
         cfg = server.cfg
-        if cfg.optimizer == "lars":  # csrc/server/sync_loop.cpp launches psx_sgd_apply_multi itself
-            raise ValueError("the native sync rounds apply plain SGD: --optimizer lars runs on the Python server")
+        if cfg.optimizer != "sgd":  # csrc/server/sync_loop.cpp launches psx_sgd_apply_multi itself
+            raise ValueError(f"the native sync rounds apply plain SGD: --optimizer {cfg.optimizer} runs on the Python "
+                             f"server")
         self.server, self.t, self.chan = server, transport, chan
         self.gs0 = server.core.global_step  # the core's step when this loop took over
         dev = server.device

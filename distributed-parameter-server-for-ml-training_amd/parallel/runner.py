@@ -142,9 +142,9 @@ def run_local_threads(cfg, steps: int, log=print, emit: bool = True) -> dict:
     more per worker on the threads, timed. Returns the server metrics plus the timed region's
     processed / accepted pushes and images per second counted over ACCEPTED pushes only."""
     assert cfg.mode == "async"
-    if cfg.optimizer == "lars":
-        raise ValueError("run_local_threads is bound to the native event loop, which applies plain SGD: "
-                         "--optimizer lars is not available here")
+    if cfg.optimizer != "sgd":
+        raise ValueError(f"run_local_threads is bound to the native event loop, which applies plain SGD: "
+                         f"--optimizer {cfg.optimizer} is not available here")
     if cfg.grad_guard:
         raise ValueError("run_local_threads is bound to the native event loop, which applies plain SGD: "
                          "--clip-norm / --skip-nonfinite are not available here")

@@ -76,6 +76,14 @@ class ParameterServer:
                 from ..ops import kernels as K
 
                 self._lars_tab = K.lars_table(layout, self.device)
+        # --optimizer adamw: element-wise, so every range of every path goes through _adamw_range
+        # (csrc/kernels/adamw.hip); state: both moments and the count of completed updates
+        self._adamw = cfg.optimizer == "adamw"
+        self.adam_m = self.adam_v = None
+        self.adam_t = 0
+        if self._adamw:
+            self.adam_m = torch.zeros_like(self.params)
+            self.adam_v = torch.zeros_like(self.params)
         # --clip-norm / --skip-nonfinite: every whole-arena update goes through _guard_update (the
         # three launches of csrc/kernels/gguard.hip, staged through agg); no parameter state, only
         # the counters: in the device state block, or in _guard_host on a CPU arena
@@ -127,7 +135,8 @@ class ParameterServer:
             self._apply_dc(grads, weight, worker_id)
             return self.finish_round_apply(self._time_end(t0))
         if grads.dtype == torch.int32:  # top-k payload (parallel/topk.py)
-            if not self.cfg.momentum and not self.cfg.weight_decay and not self._lars and not self._guard:
+            if not self.cfg.momentum and not self.cfg.weight_decay and not self._lars and not self._guard \
+                    and not self._adamw:
                 # no optimizer state: scatter straight into the fp32 master parameters
                 topk.decode_add(grads, self.params, -self.lr * weight, self._kcap)
                 self._wire_stale = True  # the bf16 image was not written by this update
@@ -144,8 +153,8 @@ class ParameterServer:
         launch on the device (the weight image, when enabled, written in the same pass); the
         torch decode into the aggregation buffer on a CPU arena. LARS: decoded into the
         aggregation buffer on either, then the dense entry of the LARS pair; the gradient guard
-        likewise (its dense entry)."""
-        if self.device.type == "cuda" and not self._lars and not self._guard:
+        likewise (its dense entry), and AdamW (the one-source fp32 form of its kernel)."""
+        if self.device.type == "cuda" and not self._lars and not self._guard and not self._adamw:
             from ..ops import kernels as K
 
             img = self.wire.img[: self.n] if self.wire is not None else None
@@ -291,7 +300,9 @@ class ParameterServer:
         self._sgd_range(g, weight, lo, hi)
 
     def _sgd_range(self, g: torch.Tensor, weight: float, lo: int, hi: int):
-        """apply_range's plain SGD form (no LARS, no guard routing)."""
+        """apply_range's plain SGD form (no LARS, no guard routing); AdamW's under --optimizer adamw."""
+        if self._adamw:
+            return self._adamw_range([g], weight, lo, hi)
         p = self.params[lo:hi]
         buf = self.momentum_buf[lo:hi] if self.momentum_buf is not None else None
         if self.device.type == "cuda":
@@ -323,6 +334,8 @@ class ParameterServer:
         if self._guard:
             self._guard_whole(lo, hi)
             return self._guard_update(list(srcs), weight)
+        if self._adamw:
+            return self._adamw_range([s[lo:hi] for s in srcs], weight, lo, hi)
         if self.device.type == "cuda":
             from ..ops import kernels as K
 
@@ -336,6 +349,49 @@ class ParameterServer:
         for s in srcs:  # fixed order, fp32 accumulation
             agg.add_(s[lo:hi].to(torch.float32))
         self.apply_range(agg, weight, lo, hi)
+
+    # ------------------------------------------------------------------ AdamW (--optimizer adamw)
+    _IMG_OF_WIRE = object()
+
+    def _adamw_range(self, srcs: list, weight: float, lo: int, hi: int, img=_IMG_OF_WIRE):
+        """The AdamW update of params[lo:hi] from sources that each hold exactly that slice (fp16 /
+        fp32 wires summed in fp32 in list order, or one dense fp32 sum), update number adam_t + 1:
+        g = weight * s; m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g g;
+        p = p (1 - lr wd) - lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps).
+        Element-wise: any range is legal, and every range of one round shares t
+        (finish_round_apply closes the round). ``img``: the bf16 image slice to write (default: the
+        weight wire's). Device: one launch of csrc/kernels/adamw.hip; CPU arena: the same formula in
+        torch fp32 from the same eight fp32 scalars (equal to a tolerance, not bit for bit)."""
+        import numpy as np
+
+        from ..ops import kernels as K
+
+        cfg = self.cfg
+        n, t = hi - lo, self.adam_t + 1
+        if n <= 0:
+            return
+        p, m, v = self.params[lo:hi], self.adam_m[lo:hi], self.adam_v[lo:hi]
+        hp = dict(beta1=cfg.adam_beta1, beta2=cfg.adam_beta2, eps=cfg.adam_eps, wd=cfg.weight_decay)
+        if self.device.type == "cuda":
+            if img is self._IMG_OF_WIRE:
+                img = self.wire.img[lo:hi] if self.wire is not None else None
+            K.adamw_apply_multi(p, [s[:n] for s in srcs], m, v, self.lr, t, gscale=weight, n=n, img=img, **hp)
+            return
+        try:
+            step_size, b1, omb1, b2, omb2, rbc2, eps, decay = K.adamw_scalars(self.lr, t, **hp)
+        except (OSError, RuntimeError, AttributeError):  # the kernel library is not loaded here
+            step_size, b1, omb1, b2, omb2, rbc2, eps, decay = K.adamw_scalars_host(self.lr, t, **hp)
+        if self.wire is not None:
+            self._wire_stale = True
+        s = torch.zeros(n, dtype=torch.float32, device=self.device)
+        for x in srcs:  # fixed order, fp32 accumulation
+            s = s + x[:n].to(torch.float32)
+        # plain element-wise fp32 ops only (no fused alpha forms): a range gives the whole round's bits
+        g = s * float(np.float32(weight))
+        m.copy_(m * b1 + g * omb1)
+        v.copy_(v * b2 + (g * g) * omb2)
+        den = v.sqrt() * rbc2 + eps
+        p.copy_(p * decay - (m / den) * step_size)
 
     # ------------------------------------------------------------------ LARS (--optimizer lars)
     def _lars_whole(self, lo: int, hi: int):
@@ -483,6 +539,8 @@ class ParameterServer:
         """Closes one update (global_step + 1). ``dt`` >= 0: its host-measured time (CPU arena);
         else the device ranges timed since the last close (deferred), or none (graph capture)."""
         self._mom_first = False
+        if self._adamw:
+            self.adam_t += 1
         if self._round_ev:
             self._ev_pending = self._ev_pending + [self._round_ev]
             self._round_ev = []
@@ -676,6 +734,8 @@ class ParameterServer:
             self._lars_update(list(srcs), res.weight)
         elif self._guard:
             self._guard_update(list(srcs), res.weight)
+        elif self._adamw:
+            self._adamw_range([s[: self.n] for s in srcs], res.weight, 0, self.n)
         elif self.device.type == "cuda":
             from ..ops import kernels as K
 
@@ -736,7 +796,8 @@ class ParameterServer:
         step = self.core.global_step
         path = path or ckpt.path_for(self.cfg.ckpt_dir, step)
         ckpt.save(path, self.layout, self.arena, self.counters, step, self.cfg.mode, self.total_workers, self.lr,
-                  self.momentum_buf, self.cfg.to_json(), dc_meansquare=self._dc_ms)
+                  self.momentum_buf, self.cfg.to_json(), dc_meansquare=self._dc_ms,
+                  adam=(self.adam_m, self.adam_v, self.adam_t) if self._adamw else None)
         self.log(f"[Checkpoint] global step {step} -> {path}")
         return path
 
@@ -765,6 +826,18 @@ class ParameterServer:
         ms = obj.get("server_optimizer_state", {}).get("dc_meansquare")
         if ms is not None and self._dc_ms is not None:
             self._dc_ms.copy_(ms.to(self.device))
+        # AdamW: both moments and the update count (absent, e.g. an SGD server's checkpoint: zero
+        # moments, the next update is t = 1)
+        if self._adamw:
+            st = obj.get("server_optimizer_state", {})
+            if st.get("adam_m") is not None and st.get("adam_v") is not None:
+                self.adam_m.copy_(st["adam_m"].to(self.device))
+                self.adam_v.copy_(st["adam_v"].to(self.device))
+                self.adam_t = int(st.get("adam_step", 0))
+            else:
+                self.adam_m.zero_()
+                self.adam_v.zero_()
+                self.adam_t = 0
         self.log(f"[Resume] restored global step {step} from {path}")
 
     # ------------------------------------------------------------------ metrics
@@ -776,6 +849,9 @@ class ParameterServer:
         m["optimizer"] = self.cfg.optimizer
         if self._lars:
             m["lars_trust_ratio"] = self.lars_trust_ratios()
+        if self._adamw:
+            m["adamw"] = {"beta1": float(self.cfg.adam_beta1), "beta2": float(self.cfg.adam_beta2),
+                          "eps": float(self.cfg.adam_eps), "steps": int(self.adam_t)}
         if self._guard:
             m["gradient_guard"] = self.guard_counters()
         if self._dc:

@@ -9,7 +9,8 @@ Here the sync round is
     push : all-to-all of the fp16 gradient wire chunks — rank r receives every rank's chunk r
            (the bytes of a reduce-scatter, without its fp16 running sum)
     apply: rank r runs the fused SGD (csrc/kernels/optim.hip sgd_apply_multi: the W chunks
-           decoded and summed in fp32 in rank order) on params[lo_r:hi_r] only, writing the
+           decoded and summed in fp32 in rank order; --optimizer adamw: csrc/kernels/adamw.hip
+           with this rank's slices of the moments) on params[lo_r:hi_r] only, writing the
            parameter image of that range (bf16 for the bf16 compute path, fp32 for fp32) and
            gathers the fp32 entries of its range that a worker needs (BN affine, FC; rank 0 also
            the BN running buffers)
@@ -178,9 +179,13 @@ class ShardedSyncChannel(WatchedRounds):
                 from ..ops import kernels as K
 
                 buf = s.momentum_buf[self.lo:self.hi] if s.momentum_buf is not None else None
-                K.sgd_apply_multi(s.params[self.lo:self.hi], [x[:n] for x in srcs], s.lr, gscale=weight,
-                                  momentum=s.cfg.momentum, wd=s.cfg.weight_decay, buf=buf, first=s._mom_first, n=n,
-                                  img=self.wire.img[self.lo:self.hi] if bf16_img else None)
+                if s.cfg.optimizer == "adamw":  # this rank's slices of the moments; every rank counts t itself
+                    s._adamw_range([x[:n] for x in srcs], weight, self.lo, self.hi,
+                                   img=self.wire.img[self.lo:self.hi] if bf16_img else None)
+                else:
+                    K.sgd_apply_multi(s.params[self.lo:self.hi], [x[:n] for x in srcs], s.lr, gscale=weight,
+                                      momentum=s.cfg.momentum, wd=s.cfg.weight_decay, buf=buf, first=s._mom_first,
+                                      n=n, img=self.wire.img[self.lo:self.hi] if bf16_img else None)
                 if not bf16_img:
                     self.wire.img[self.lo:self.hi].copy_(s.params[self.lo:self.hi])
             else:

@@ -9,6 +9,7 @@ de-facto wire layout is the FetchReply payload ``{state_dict_name: ndarray}``
      "global_step": int, "mode": str, "total_workers": int, "lr": float,
      "server_optimizer_state": {"momentum": tensor | None,
                                 "dc_meansquare": tensor   # optional: --dc-adaptive mean square
+                                "adam_m", "adam_v": tensor, "adam_step": int   # optional: --optimizer adamw
                                 }, "config": json str}
 
 Written with torch.save to a temp file + atomic rename; loaded with
@@ -27,7 +28,7 @@ FORMAT = "psx-ckpt-v1"
 
 def save(path: str, layout, arena: torch.Tensor, counters: torch.Tensor | None, global_step: int, mode: str,
          total_workers: int, lr: float, momentum_buf: torch.Tensor | None = None, config_json: str = "",
-         dc_meansquare: torch.Tensor | None = None) -> str:
+         dc_meansquare: torch.Tensor | None = None, adam: tuple | None = None) -> str:
     sd = layout.to_state_dict(arena, counters)
     obj = {
         "format": FORMAT,
@@ -41,6 +42,9 @@ def save(path: str, layout, arena: torch.Tensor, counters: torch.Tensor | None, 
     }
     if dc_meansquare is not None:  # optional key: checkpoints without it load, ms starts at zero
         obj["server_optimizer_state"]["dc_meansquare"] = dc_meansquare.detach().cpu()
+    if adam is not None:  # optional keys (m, v, completed updates): without them the moments start at zero
+        m, v, step = adam
+        obj["server_optimizer_state"].update(adam_m=m.detach().cpu(), adam_v=v.detach().cpu(), adam_step=int(step))
     d = os.path.dirname(os.path.abspath(path))
     os.makedirs(d, exist_ok=True)
     tmp = path + ".tmp"

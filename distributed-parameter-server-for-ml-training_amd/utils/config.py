@@ -11,8 +11,8 @@ Keeps every flag and environment variable of the reference with the same default
 
 and adds the MI355X-native knobs: --gpus/--nproc, --codec, --topk-ratio,
 --dtype, --momentum/--weight-decay (server optimizer, default 0 = reference parity),
---optimizer {sgd,lars} with --lars-trust/--lars-eps, --dc-lambda/--dc-adaptive (async delay
-compensation), --clip-norm/--skip-nonfinite (global-norm clipping, non-finite guard), --model,
+--optimizer {sgd,lars,adamw} with --lars-trust/--lars-eps and --adam-beta1/--adam-beta2/--adam-eps,
+--dc-lambda/--dc-adaptive (async delay compensation), --clip-norm/--skip-nonfinite (global-norm clipping, non-finite guard), --model,
 --synthetic, --ckpt-every/--resume, --sync-semantics {barrier,reference}, --topology.
 Precedence: explicit CLI flag > JSON config file (--config) > environment > default.
 """
@@ -66,6 +66,14 @@ class PSConfig:
     optimizer: str = "sgd"
     lars_trust: float = 0.001
     lars_eps: float = 1e-8
+    # adamw (csrc/kernels/adamw.hip): Adam moments with bias correction and the decoupled weight
+    # decay of torch.optim.AdamW, p <- p (1 - lr wd) - lr mhat / (sqrt(vhat) + adam_eps); weight_decay
+    # applies to every trainable element, 0 = plain Adam. Element-wise, so unlike lars it also runs
+    # on bucketed overlapped rounds and on the sharded server; momentum must be 0 (beta1 is the
+    # momentum). Python server only: no native loops, graph round or elastic shrink.
+    adam_beta1: float = 0.9
+    adam_beta2: float = 0.999
+    adam_eps: float = 1e-8
     # async delay compensation (DC-ASGD, csrc/kernels/dcasgd.hip): the server keeps the parameters
     # each worker last fetched (bak) and applies g + lam * g * g * (w - bak) in place of g.
     # dc_lambda 0 = off; dc_adaptive: lam = dc_lambda / sqrt(ms + dc_eps) with ms the running mean
@@ -139,8 +147,15 @@ class PSConfig:
             raise ValueError(f"--codec must be none, fp16, q8 or topk, got {self.codec!r}")
         if self.topology not in ("colocated", "dedicated", "sharded"):
             raise ValueError(f"--topology must be colocated, dedicated or sharded, got {self.topology!r}")
-        if self.optimizer not in ("sgd", "lars"):
-            raise ValueError(f"--optimizer must be sgd or lars, got {self.optimizer!r}")
+        if self.optimizer not in ("sgd", "lars", "adamw"):
+            raise ValueError(f"--optimizer must be sgd, lars or adamw, got {self.optimizer!r}")
+        if self.optimizer == "adamw":
+            if not (0.0 <= self.adam_beta1 < 1.0) or not (0.0 <= self.adam_beta2 < 1.0):
+                raise ValueError("--optimizer adamw: --adam-beta1 and --adam-beta2 must be in [0, 1)")
+            if not self.adam_eps > 0.0:
+                raise ValueError("--optimizer adamw: --adam-eps must be > 0")
+            if self.momentum:
+                raise ValueError("--optimizer adamw: --adam-beta1 is the momentum, --momentum must be 0")
         if self.optimizer == "lars":
             if not (self.lars_trust > 0.0) or self.lars_eps < 0.0:
                 raise ValueError("--optimizer lars: --lars-trust must be > 0 and --lars-eps >= 0")
@@ -157,15 +172,16 @@ class PSConfig:
         if self.dc_lambda > 0.0:
             if self.mode != "async":  # every sync push has staleness 0: nothing to compensate
                 raise ValueError("--dc-lambda compensates gradient staleness: --mode async only")
-            if self.optimizer == "lars":
-                raise ValueError("--dc-lambda runs on the SGD server update: not with --optimizer lars")
+            if self.optimizer != "sgd":
+                raise ValueError(f"--dc-lambda runs on the SGD server update: not with --optimizer {self.optimizer}")
         if not self.clip_norm >= 0.0:
             raise ValueError("--clip-norm must be >= 0")
         if self.clip_norm > 0.0:
             self.skip_nonfinite = True
         if self.grad_guard:
-            if self.optimizer == "lars":
-                raise ValueError("--clip-norm / --skip-nonfinite run on the SGD server update: not with --optimizer lars")
+            if self.optimizer != "sgd":
+                raise ValueError(f"--clip-norm / --skip-nonfinite run on the SGD server update: not with --optimizer "
+                                 f"{self.optimizer}")
             if self.dc_lambda > 0.0:
                 raise ValueError("--clip-norm / --skip-nonfinite run on the SGD server update: not with --dc-lambda")
             if self.topology == "sharded":  # no shard sees the whole gradient
@@ -213,7 +229,8 @@ class PSConfig:
         with and the round qualifies (sync, one push per batch, dense wire, rank-0 server). The
         error-feedback codecs (q8, topk) encode the whole gradient at once, and --optimizer lars
         and the gradient guard (--clip-norm / --skip-nonfinite) need a norm of the whole gradient
-        before the first element moves: no bucketed rounds."""
+        before the first element moves: no bucketed rounds. --optimizer adamw is element-wise and
+        stays eligible."""
         if self.overlap is None:
             self.overlap = (world > 1 and self.mode == "sync" and max(1, self.sync_steps) == 1
                             and self.dense_wire and self.topology != "sharded" and self.optimizer != "lars"
@@ -260,11 +277,15 @@ def add_arguments(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
       help="worker compute precision: fp32 (reference, default) or bf16 (fast path)")
     A("--momentum", type=float, default=None)
     A("--weight-decay", type=float, default=None)
-    A("--optimizer", choices=["sgd", "lars"], default=None,
-      help="server optimizer: sgd (default) or lars (layer-wise trust ratio on tensors with ndim > 1; "
-           "uses --momentum / --weight-decay; Python server, whole-arena updates)")
+    A("--optimizer", choices=["sgd", "lars", "adamw"], default=None,
+      help="server optimizer: sgd (default), lars (layer-wise trust ratio on tensors with ndim > 1; "
+           "uses --momentum / --weight-decay; Python server, whole-arena updates) or adamw (Adam with "
+           "decoupled --weight-decay; Python server, also bucketed and sharded rounds)")
     A("--lars-trust", type=float, default=None, help="LARS trust coefficient (default 0.001)")
     A("--lars-eps", type=float, default=None, help="LARS denominator epsilon (default 1e-8)")
+    A("--adam-beta1", type=float, default=None, help="AdamW first-moment decay (default 0.9)")
+    A("--adam-beta2", type=float, default=None, help="AdamW second-moment decay (default 0.999)")
+    A("--adam-eps", type=float, default=None, help="AdamW denominator epsilon (default 1e-8)")
     A("--dc-lambda", type=float, default=None,
       help="async delay compensation (DC-ASGD): apply g + lambda*g*g*(w - w_at_fetch); 0 = off (default)")
     A("--dc-adaptive", action="store_true", default=None,

@@ -18,6 +18,9 @@
                       trust ratio scales every tensor's step to lr * 0.001 * |w| / |g|, so its lr is
                       not comparable to the SGD curves' 0.05); also compared against ``psx_fp32``
                       (``lars_vs_psx_fp32``), next to the torch seed-to-seed spread.
+* ``psx_fp32_adamw``  psx_fp32 with the AdamW server optimizer (--optimizer adamw, lr 1e-3, weight decay
+                      1e-2, fp16 wire), its own run: recorded next to ``psx_fp32`` and compared with
+                      it (``adamw_vs_psx_fp32``), not a parity claim and not asserted.
 * ``psx_bf16``        the bf16 HIP engine (fast path), fp16 wire, bf16conv fetch.
 * ``psx_fp32_reference_bn`` psx_fp32 with the reference's BN semantics (no --bn-sync): same
                       training curve, but the evaluation runs on never-learned running statistics.
@@ -207,6 +210,7 @@ def main():
     test = DeviceDataset.synthetic_hard(args.test, device=DEV, offset=10_000_000)
     runs = {}
     lars = dict(optimizer="lars", lr=args.lars_lr, momentum=0.9, weight_decay=5e-4)
+    adamw = dict(optimizer="adamw", lr=1e-3, weight_decay=1e-2)
     only = [x for x in args.only.split(",") if x]
     for name, fn in (("torch_fp32", lambda: run_torch(args, train, test, 0)),
                      ("torch_fp32_init1", lambda: run_torch(args, train, test, 1)),
@@ -214,6 +218,7 @@ def main():
                      ("psx_fp32_wire32", lambda: run_psx(args, train, test, "fp32", "none")),
                      ("psx_fp32_q8", lambda: run_psx(args, train, test, "fp32", "q8")),
                      ("psx_fp32_lars", lambda: run_psx(args, train, test, "fp32", "fp16", **lars)),
+                     ("psx_fp32_adamw", lambda: run_psx(args, train, test, "fp32", "fp16", **adamw)),
                      ("psx_bf16", lambda: run_psx(args, train, test, "bf16", "fp16")),
                      ("psx_fp32_reference_bn", lambda: run_psx(args, train, test, "fp32", "fp16", bn_sync=False))):
         if only and name not in only and name != "torch_fp32":
@@ -234,7 +239,7 @@ def main():
                      "test_acc_diff_pp": r["test_acc"] - runs["torch_fp32"]["test_acc"]}
         print(f"  vs torch_fp32: {name:18s} {json.dumps(cmp[name])}", flush=True)
     vs_psx = {}
-    for name in ("psx_fp32_q8", "psx_fp32_lars"):
+    for name in ("psx_fp32_q8", "psx_fp32_lars", "psx_fp32_adamw"):
         if name not in runs or "psx_fp32" not in runs:
             continue
         d = smooth(runs[name]["loss"], args.window) - smooth(runs["psx_fp32"]["loss"], args.window)
@@ -253,7 +258,8 @@ def main():
     out = {"config": vars(args), "data": "synthetic_hard: 4x4 class prototypes (std 12) + pixel noise (std 64), "
                                           "20% label noise, 100 classes",
            "runs": runs, "vs_torch_fp32": cmp, "q8_vs_psx_fp32": vs_psx.get("psx_fp32_q8"),
-           "lars_vs_psx_fp32": vs_psx.get("psx_fp32_lars"), "w4_sync": w4}
+           "lars_vs_psx_fp32": vs_psx.get("psx_fp32_lars"), "adamw_vs_psx_fp32": vs_psx.get("psx_fp32_adamw"),
+           "w4_sync": w4}
     with open(os.path.join(args.out, "convergence_parity.json"), "w") as f:
         json.dump(out, f)
     try:
