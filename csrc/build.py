@@ -52,6 +52,14 @@ def _run(cmd):
 FILE_FLAGS = {"wino_fused.hip": ["-fno-slp-vectorize"], "wino_wgrad.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
 
 
+def kernel_flags(opt, src=None) -> list:
+    """hipcc flags of one csrc/kernels/*.hip compile (FILE_FLAGS of ``src`` included); also what
+    scripts/prof/kernel_resources.py compiles with."""
+    flags = [f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
+             "-Wno-unused-variable", "-munsafe-fp-atomics", "-I", os.path.join(HERE, "kernels")] + list(opt)
+    return flags + (FILE_FLAGS.get(os.path.basename(src), []) if src else [])
+
+
 def build(jobs: int = 8, debug: bool = False, verbose: bool = False) -> dict:
     os.makedirs(OUT, exist_ok=True)
     os.makedirs(OBJ, exist_ok=True)
@@ -61,8 +69,7 @@ def build(jobs: int = 8, debug: bool = False, verbose: bool = False) -> dict:
     r_hdrs = glob.glob(os.path.join(HERE, "runtime", "*.h")) + glob.glob(os.path.join(HERE, "runtime", "*.hpp"))
     r_srcs = sorted(glob.glob(os.path.join(HERE, "runtime", "*.cpp")))
 
-    hip_flags = [f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
-                 "-Wno-unused-variable", "-munsafe-fp-atomics", "-I", os.path.join(HERE, "kernels")] + opt
+    hip_flags = kernel_flags(opt)
     cxx_flags = ["-std=c++17", "-fPIC", "-Wall", "-pthread", "-I", os.path.join(HERE, "runtime")] + opt
 
     jobs_list = []

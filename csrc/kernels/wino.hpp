@@ -15,6 +15,24 @@ PSX_DEV void wino_bt6(const float (&d)[6], float (&r)[6]) {
   r[5] = 4.f * d[1] - 5.f * d[3] + d[5];
 }
 
+// wino_bt6 for wino_fused.hip, with its multiply-adds written out and no contraction left to
+// hipcc. In r[0] and r[5] either product of a x - b y can be the fused one, and which one hipcc
+// picks depends on the code around the transform: in wino_fused.hip it fused 4 d0 - (5 d2) in the
+// row pass and (4 d0) - 5 d2 in the column pass (COL), and chose differently once the padding
+// select there became a bit mask. These are the forms that kernel has always computed with, so its
+// outputs stay bit-identical from build to build. Do NOT merge this with wino_bt6: wino.hip's
+// kernels compute with whatever hipcc contracts there, and either merge changes somebody's bits.
+template <bool COL>
+PSX_DEV void wino_bt6_fused(const float (&d)[6], float (&r)[6]) {
+#pragma clang fp contract(off)
+  r[0] = (COL ? __builtin_fmaf(-5.f, d[2], 4.f * d[0]) : __builtin_fmaf(4.f, d[0], -5.f * d[2])) + d[4];
+  r[1] = __builtin_fmaf(-4.f, d[1] + d[2], d[3]) + d[4];
+  r[2] = __builtin_fmaf(4.f, d[1] - d[2], -d[3]) + d[4];
+  r[3] = __builtin_fmaf(2.f, d[3] - d[1], -d[2]) + d[4];
+  r[4] = __builtin_fmaf(2.f, d[1] - d[3], -d[2]) + d[4];
+  r[5] = __builtin_fmaf(4.f, d[1], -5.f * d[3]) + d[5];
+}
+
 PSX_DEV void wino_at6(const float (&m)[6], float (&o)[4]) {
   const float a = m[1] + m[2], b = m[1] - m[2], c = m[3] + m[4], d = m[3] - m[4];
   o[0] = m[0] + a + c;

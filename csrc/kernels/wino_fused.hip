@@ -23,13 +23,30 @@
 // one k-step ahead. Waves 0-3 transform group g + 1 first (patch loaded during group g - 1) while
 // waves 4-7 already multiply group g; the group buffer is double-buffered. The group loop is fully
 // unrolled (4 or 8 groups: 64 / 128 input channels), which also keeps hipcc from copying the
-// loop-carried accumulators between register files every group.
+// loop-carried accumulators between register files every group; its last iteration transforms
+// nothing and its last two load no patch (no dummy group past the end), and hipcc still moves no
+// accumulators.
+//
+// What a launch is, is decided at compile time: besides the epilogue variant, the input kind IN
+// (PLAIN: the patch as loaded; BNIN: the previous layer's BN + ReLU folded in; BWDIN: the BN
+// backward apply folded in, reads ybn) and HASV (the V side output) are template parameters, and
+// psx_wino_fused's tables hold only the combinations a launch can have (52 instantiations). A PLAIN
+// launch has no coefficient table, no fma / max per patch value and no second patch; without HASV
+// the V descriptor, offsets and stores do not exist. The zero padding is a bit mask (row mask &
+// column mask) on the value, not 36 selects whose conditions hipcc kept in 72 SGPRs across the
+// loop: PLAIN instantiations have no SGPR spills, BNIN 12-16 (all in the BN finalize prologue),
+// BWDIN 26-33 (it keeps the selects: no VGPRs left for the masks), against 93-110 before; no
+// instantiation spills VGPRs or uses scratch (tests/test_kernel_resources_cpu.py,
+// scripts/prof/kernel_resources.py). Two things are as they are because hipcc otherwise spills
+// VGPRs: BWDIN tests its flag at run time, and the B load past the last k-step (a re-load) stays.
 //
 // Epilogue: per tile the row pass Z = (M rows) A of the wave's 3 rows, its share of y = A^T M A,
 // the partner wave's share of two of the four tiles through LDS, then (same contract as wino.hip
 // wino_out_kernel) forward (+ residual) with BN slot sums of y (shifted), or data gradient with the
 // consumer BN's backward sums (ReLU mask from o or from the affine, one or two BNs) and the masked
-// store; deterministic mode through the slab (DetRed). V (nullable): the forward also stores the
+// store; deterministic mode through the slab (DetRed). The epilogue operands (res, y1, o, y2) of the
+// lane's first output tile are loaded before the last group's MFMAs, into the registers the patch
+// no longer needs (0.5-1.8 us per data-gradient launch). V (HASV): the forward also stores the
 // transformed input [36][T][C] for the Winograd weight gradient (wino.hip psx_wino_wgrad).
 #include "bnfin.hpp"
 #include "common.hpp"
@@ -47,6 +64,12 @@
 #endif
 #ifndef PSX_WF_SWZ
 #define PSX_WF_SWZ 1
+#endif
+// 1: the first output tile's epilogue operands (res, y1, o, y2) are loaded before the last group's
+// MFMAs; 0: every epilogue load after the group loop; 2 (A/B builds): both tiles' operands early
+// (the residual + mask-from-o + two-BN variants, 2 x 64 values, then spill 22-23 VGPRs)
+#ifndef PSX_WF_EARLY
+#define PSX_WF_EARLY 1
 #endif
 
 namespace psx {
@@ -73,7 +96,11 @@ struct WinoFusedArgs {
   int xbytes, ubytes, vbytes, ybytes;
 };
 
-template <int GG, bool RES, bool BWD, bool MAFF, bool TWO>
+// input kind of a launch (template parameter IN): the patch as loaded, the previous layer's
+// forward BN + ReLU folded in (bnpart), or the BN-backward apply folded in (ybn / bpart)
+constexpr int kWfPlain = 0, kWfBnIn = 1, kWfBwdIn = 2;
+
+template <int GG, bool RES, bool BWD, bool MAFF, bool TWO, int IN, bool HASV>
 __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, WinoBnFin fin, WinoBwdStats bs,
                                                             DetRed det, BnBwdFin bfin) {
   // [buffer][k-step][slot][lane]: slot 5h + i (i < 4) = points 18h + 4i .. +3, slot 5h + 4 = points
@@ -88,14 +115,14 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
   const int tb = id / a.nkb, kb = id - tb * a.nkb;
   const int H = a.H, W = a.W, C = a.C, K = a.K;
   const int tw = W >> 2, tpi = (H >> 2) * tw;
-  const bool bnin = a.bnpart != nullptr;
-  // BN-backward fold (data gradient whose input dy = BNbwd(dz, y) was never written): x is dz,
-  // the operand is k1 dz + k2 y + k3 with the coefficients finalized here from the slot sums
-  const bool bwdin = a.bpart != nullptr;
-  // the transform applies max(x * aff0 + aff1, lo) unconditionally (one branch-free group body):
-  // identity (1, 0, -inf) without a folded BN
-  const float lo = bnin ? 0.f : -__builtin_inff();
-  if (bwdin) {
+  // BNIN: the transform applies max(x * aff0 + aff1, 0). BWDIN (data gradient whose input dy =
+  // BNbwd(dz, y) was never written): x is dz, the operand is k1 dz + k2 y + k3 with the coefficients
+  // finalized here from the slot sums. PLAIN: the patch value as loaded, no coefficients at all
+  constexpr bool bnin = IN == kWfBnIn;
+  // In a BWDIN instantiation the flag stays a run-time value (always true): with a compile-time one
+  // hipcc schedules the y loads and the apply across the group body and spills 7-36 VGPRs to scratch
+  const bool bwdin = IN == kWfBwdIn && a.bpart != nullptr;
+  if constexpr (IN == kWfBwdIn) {
     for (int c = threadIdx.x; c < C; c += 512) {
       float k1, k2, k3;
       double sdz, sxh;
@@ -117,12 +144,7 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
         }
       }
     }
-  } else if (!bnin) {
-    for (int c = threadIdx.x; c < C; c += 512) {
-      aff[0][c] = 1.f;
-      aff[1][c] = 0.f;
-    }
-  } else {  // BN finalize of the input channels (wino.hip wino_in_kernel), all C of them
+  } else if constexpr (bnin) {  // BN finalize of the input channels (wino.hip wino_in_kernel), all C of them
     for (int c = threadIdx.x; c < C; c += 512) {
       const double s = slot_sum<PSX_STAT_SLOTS>(a.bnpart, c, 2 * (size_t)C, fin.det);
       const double ss = slot_sum<PSX_STAT_SLOTS>(a.bnpart, (size_t)C + c, 2 * (size_t)C, fin.det);
@@ -146,7 +168,7 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
       }
     }
   }
-  __syncthreads();
+  if constexpr (IN != kWfPlain) __syncthreads();
 
   // ---- transform role (waves 0-3, wave kq = k-step kq of a group): lane = (tile l&15, channel l>>4)
   // (tiles 4 kq .. 4 kq + 3 x the group's 16 channels: a patch load is 4 runs of 64 contiguous
@@ -171,16 +193,16 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
     }
   }
   const auto xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, a.xbytes, 0x00020000);
-  const auto ybr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.ybn), 0, bwdin ? a.xbytes : 0, 0x00020000);
+  const auto ybr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.ybn), 0, bwdin ? a.xbytes : 0, 0x00020000);  // BWDIN only
   const auto ur = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.U), 0, a.ubytes, 0x00020000);
   const int S4 = C >> 2;  // MFMA k-steps
   // B operand of wave (kq, h): k-step s at ubase + s * 10 KB, its slots 5h .. 5h + 4
   const int ubase = ((kb * 4 + kq) * S4 * 10 + h * 5) * 1024;
   constexpr int G = GG;  // 16-channel groups (C / 16): the group loop is fully unrolled
-  // V side output through a buffer descriptor: stores of the pipeline's one dummy transform (past
-  // the last group) go to a zero-record descriptor and are dropped
-  const auto vr = __builtin_amdgcn_make_buffer_rsrc(a.V, 0, a.V ? a.vbytes : 0, 0x00020000);
-  const auto vnull = __builtin_amdgcn_make_buffer_rsrc(a.V, 0, 0, 0x00020000);
+  // V side output (HASV) through a buffer descriptor. One channel block writes V (the others'
+  // transforms are the same values: the 16x16x128 forward, two blocks, stored every value twice):
+  // the other blocks' descriptor has no records and their stores are dropped
+  const auto vr = __builtin_amdgcn_make_buffer_rsrc(a.V, 0, (HASV && kb == 0) ? a.vbytes : 0, 0x00020000);
   const int voff = (t * C + cl) * 4;
 
   // LDS image unit of (k-step q, A-operand lane u): XOR-swizzled within the k-step's 1 KB slot
@@ -205,10 +227,14 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
           yb[r * 6 + s] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ybr, rowoff[r] + coloff[s], so, 0));
     }
   };
-  auto xform = [&](int g, int p, bool real) {
+  auto xform = [&](int g, int p) {
     if constexpr ((PSX_WF_PROBE & 32) != 0) return;
     const int ch0 = g * 16;  // wave-uniform
-    const float sc = aff[0][ch0 + cl], sh = aff[1][ch0 + cl];
+    float sc = 1.f, sh = 0.f;
+    if constexpr (IN != kWfPlain) {
+      sc = aff[0][ch0 + cl];
+      sh = aff[1][ch0 + cl];
+    }
     float e[36];
     if (bwdin) {  // dy = k1 dz + k2 y + k3 (k2 in aff[2]), padding stays zero
       const float k2 = aff[2][ch0 + cl];
@@ -217,24 +243,41 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
 #pragma unroll
         for (int s = 0; s < 6; ++s) d[r * 6 + s] = wino_bwd_apply(d[r * 6 + s], yb[r * 6 + s], sc, k2, sh);
     }
+    // zero padding stays zero after BN + ReLU: the value's bits ANDed with an all-ones / zero row and
+    // column mask (the same bits as a select of v or 0.f). As 36 selects hipcc kept the 36
+    // conditions as SGPR pairs across every group: 72 of the 93-110 SGPR spills, 2 v_readlane each use.
+    // The empty asm keeps the masks plain VGPR values (no fold back into selects). BWDIN keeps the
+    // selects: at 245-253 VGPRs the 12 masks push it into 48-130 VGPR spills, and its run-time
+    // branches already hold hipcc back from hoisting the conditions (26-33 SGPR spills)
+    unsigned mr[6], mc[6];
+#pragma unroll
+    for (int r = 0; r < 6 && IN != kWfBwdIn; ++r) {
+      mr[r] = (unsigned)__builtin_amdgcn_sbfe((int)okr, r, 1);
+      mc[r] = (unsigned)__builtin_amdgcn_sbfe((int)okc, r, 1);
+      asm("" : "+v"(mr[r]));
+      asm("" : "+v"(mc[r]));
+    }
 #pragma unroll
     for (int r = 0; r < 6; ++r)
 #pragma unroll
       for (int s = 0; s < 6; ++s) {
-        const float v = bwdin ? d[r * 6 + s] : fmaxf(d[r * 6 + s] * sc + sh, lo);
-        e[r * 6 + s] = ((okr >> r) & (okc >> s) & 1u) ? v : 0.f;  // zero padding stays zero after BN + ReLU
+        const float v = bnin ? fmaxf(d[r * 6 + s] * sc + sh, 0.f) : d[r * 6 + s];
+        if constexpr (IN != kWfBwdIn)
+          e[r * 6 + s] = __uint_as_float(__float_as_uint(v) & mr[r] & mc[s]);
+        else
+          e[r * 6 + s] = ((okr >> r) & (okc >> s) & 1u) ? v : 0.f;
       }
 #pragma unroll
     for (int s = 0; s < 6; ++s) {  // columns: B^T d
       float col[6] = {e[s], e[6 + s], e[12 + s], e[18 + s], e[24 + s], e[30 + s]}, o[6];
-      wino_bt6(col, o);
+      wino_bt6_fused<true>(col, o);
 #pragma unroll
       for (int r = 0; r < 6; ++r) e[r * 6 + s] = o[r];
     }
 #pragma unroll
     for (int r = 0; r < 6; ++r) {  // rows: (B^T d) B
       float row[6] = {e[r * 6], e[r * 6 + 1], e[r * 6 + 2], e[r * 6 + 3], e[r * 6 + 4], e[r * 6 + 5]}, o[6];
-      wino_bt6(row, o);
+      wino_bt6_fused<false>(row, o);
 #pragma unroll
       for (int s = 0; s < 6; ++s) e[r * 6 + s] = o[s];
     }
@@ -247,13 +290,11 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
       }
       vb[p][qa][5 * hh + 4][swz(qa, la)] = (f32x4){e[18 * hh + 16], e[18 * hh + 17], 0.f, 0.f};
     }
-    // one channel block writes V (the others' transforms are the same values): the 16x16x128 forward
-    // (two blocks) stored every value twice
-    const auto rs = (real && kb == 0) ? vr : vnull;
-    if ((PSX_WF_PROBE & 8) == 0 && a.V)  // the stores cost ~4 us on 32x32x64 even when dropped
+    if constexpr (HASV && (PSX_WF_PROBE & 8) == 0) {  // the stores cost ~4 us on 32x32x64 even when dropped
 #pragma unroll
-    for (int b = 0; b < 36; ++b)
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e[b]), rs, voff, (b * a.T * C + ch0) * 4, 0);
+      for (int b = 0; b < 36; ++b)
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e[b]), vr, voff, (b * a.T * C + ch0) * 4, 0);
+    }
   };
 
   // acc[m]: local point m = 0..17 of this wave's half (point 18h + m)
@@ -280,15 +321,15 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
   for (int i = 0; i < UD; ++i) load_u(i < S4 ? i : S4 - 1, i);
   if (h == 0) {
     load_patch(0);
-    xform(0, 0, true);
-    load_patch(G > 1 ? 1 : 0);
+    xform(0, 0);
+    if constexpr (G > 1) load_patch(1);
   }
   __syncthreads();
   // Per group g: waves 0-3 first transform group g + 1 (patch loaded during the previous group)
   // into the other buffer and issue the patch loads of g + 2, while waves 4-7 — the other wave on
   // each SIMD — already run their MFMAs of g; then waves 0-3 run theirs. The MFMA pipe sees 72 + 72
-  // MFMAs per SIMD and group with the transform in between hidden. The group past the last is a
-  // dummy (clamped loads, dropped V stores, its LDS image never read).
+  // MFMAs per SIMD and group with the transform in between hidden. The last group's iteration
+  // transforms nothing and the last two load no patch (the loop is unrolled: compile-time conditions).
   f32x4 an[4];
   float2 ah;
   auto load_a = [&](int p, int q) {
@@ -302,12 +343,57 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
     for (int i = 0; i < 4; ++i) an[i] = vb[p][q][5 * h + i][swz(q, l)];
     ah = *reinterpret_cast<const float2*>(&vb[p][q][5 * h + 4][swz(q, l)]);
   };
+  // Epilogue operands (res, y1, o, y2) of the lane's output pixels: tile ii of its two, 16 pixels,
+  // channel k. The first tile's are issued before the last group's MFMAs (PSX_WF_EARLY; the patch
+  // registers are free by then), the second tile's in the epilogue.
+  const int k = kb * kWfK + kq * 16 + (l & 15);
+  constexpr bool bwd = BWD, two = BWD && TWO;
+  const int ybytes = a.ybytes;
+#ifdef PSX_WF_RES_BUF
+  const auto rr_ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res), 0, RES ? ybytes : 0, 0x00020000);
+#endif
+  const auto y1r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bs.y1), 0, bwd ? ybytes : 0, 0x00020000);
+  const auto orr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bs.o), 0, (bwd && !MAFF) ? ybytes : 0,
+                                                     0x00020000);
+  const auto y2r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bs.y2), 0, two ? ybytes : 0, 0x00020000);
+  float rv[2][16], y1v[2][16], ov[2][16], y2v[2][16];
+  auto out_base = [&](int ii) {
+    const int tt = tb * kWfT + 4 * (l >> 4) + 2 * h + ii;
+    const int n = tt / tpi, rem = tt - n * tpi, ti = rem / tw, tj = rem - ti * tw;
+    return ((((n * H + 4 * ti) * W + 4 * tj) * K) + k) * 4;
+  };
+  auto load_epi = [&](int ii) {
+    const int base = out_base(ii);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int so = ((e >> 2) * W + (e & 3)) * K * 4;
+      // the residual through a flat load: its buffer descriptor's 4 SGPRs pushed the residual +
+      // data-gradient variants into SGPR spills held in VGPR lanes and then 25-144 VGPR spills to
+      // scratch (113 vs 66 us per 32x32x64 call, profiles/README.md round-5 leads)
+#ifdef PSX_WF_RES_BUF  // A/B builds: the buffer load
+      if constexpr (RES) rv[ii][e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr_, base, so, 0));
+#else
+      if constexpr (RES) rv[ii][e] = a.res[(base + so) >> 2];
+#endif
+      if constexpr (bwd) {
+        y1v[ii][e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(y1r, base, so, 0));
+        if constexpr (!MAFF) ov[ii][e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(orr, base, so, 0));
+        if constexpr (two) y2v[ii][e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(y2r, base, so, 0));
+      }
+    }
+  };
+  constexpr bool early = PSX_WF_EARLY && (RES || BWD);
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     const int p = g & 1;
+    if constexpr (early)
+      if (g == G - 1) {
+        load_epi(0);
+        if constexpr (PSX_WF_EARLY > 1) load_epi(1);
+      }
     if (h == 0) {
-      xform(g + 1, p ^ 1, g + 1 < G);
-      load_patch(g + 2 < G ? g + 2 : G - 1);
+      if (g + 1 < G) xform(g + 1, p ^ 1);
+      if (g + 2 < G) load_patch(g + 2);
     }
     if constexpr ((PSX_WF_PF & 2) != 0) load_a(p, 0);
 #pragma unroll
@@ -399,8 +485,6 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
     for (int j = 0; j < 4; ++j) yv[e >> 4][(e & 15) + j] += t4[j];
   }
 
-  const int k = kb * kWfK + kq * 16 + (l & 15);
-  constexpr bool bwd = BWD, two = BWD && TWO;
   float m1 = 0.f, i1 = 0.f, m2 = 0.f, i2 = 0.f, msc = 0.f, msh = 0.f;
   if constexpr (bwd) {
     m1 = bs.saved1[k];
@@ -417,56 +501,29 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
   const float kshift = (!bwd && a.sshift) ? a.sshift[k] : 0.f;  // forward statistics: shifted sums
   // the output-sized tensors through buffer descriptors: 32-bit lane offsets, the pixel step in
   // the (uniform) soffset
-  const int ybytes = a.ybytes;
   const auto yr = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, ybytes, 0x00020000);
-#ifdef PSX_WF_RES_BUF
-  const auto rr_ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res), 0, RES ? ybytes : 0, 0x00020000);
-#endif
-  const auto y1r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bs.y1), 0, bwd ? ybytes : 0, 0x00020000);
-  const auto orr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bs.o), 0, (bwd && !MAFF) ? ybytes : 0,
-                                                     0x00020000);
-  const auto y2r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bs.y2), 0, two ? ybytes : 0, 0x00020000);
   const bool mstore = bwd && bs.mask_store;
   float s1 = 0.f, s2 = 0.f, s3 = 0.f;
 #pragma unroll
   for (int ii = 0; ii < 2; ++ii) {
-    const int tt = tb * kWfT + 4 * (l >> 4) + 2 * h + ii;
-    const int n = tt / tpi, rem = tt - n * tpi, ti = rem / tw, tj = rem - ti * tw;
-    const int base = ((((n * H + 4 * ti) * W + 4 * tj) * K) + k) * 4;
-    float rv[16], y1v[16], ov[16], y2v[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int so = ((e >> 2) * W + (e & 3)) * K * 4;
-      // the residual through a flat load: its buffer descriptor's 4 SGPRs pushed the residual +
-      // data-gradient variants into SGPR spills held in VGPR lanes and then 25-144 VGPR spills to
-      // scratch (113 vs 66 us per 32x32x64 call, profiles/README.md round-5 leads)
-#ifdef PSX_WF_RES_BUF  // A/B builds: the buffer load
-      if constexpr (RES) rv[e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr_, base, so, 0));
-#else
-      if constexpr (RES) rv[e] = a.res[(base + so) >> 2];
-#endif
-      if constexpr (bwd) {
-        y1v[e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(y1r, base, so, 0));
-        if constexpr (!MAFF) ov[e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(orr, base, so, 0));
-        if constexpr (two) y2v[e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(y2r, base, so, 0));
-      }
-    }
+    const int base = out_base(ii);
+    if (!(early && (ii == 0 || PSX_WF_EARLY > 1))) load_epi(ii);
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int so = ((e >> 2) * W + (e & 3)) * K * 4;
       float v = yv[ii][e];
-      if constexpr (RES) v += rv[e];
+      if constexpr (RES) v += rv[ii][e];
       if constexpr (bwd) {
-        const float y1 = y1v[e];
+        const float y1 = y1v[ii][e];
         bool pos;
         if constexpr (MAFF)
           pos = y1 * msc + msh > 0.f;
         else
-          pos = ov[e] > 0.f;
+          pos = ov[ii][e] > 0.f;
         const float dz = pos ? v : 0.f;
         s1 += dz;
         s2 += dz * (y1 - m1) * i1;
-        if constexpr (two) s3 += dz * (y2v[e] - m2) * i2;
+        if constexpr (two) s3 += dz * (y2v[ii][e] - m2) * i2;
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mstore ? dz : v), yr, base, so, 0);
       } else {
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yr, base, so, 0);
@@ -524,6 +581,8 @@ int psx_wino_fused_ok(int N, int H, int W, int C, int K) {
 // ybn / bpart / bbfin (nullable, data gradient): x is dz and the operand is the BN backward
 // k1 dz + k2 ybn + k3 of the BN whose backward sums are bpart (the BN-backward apply folded in;
 // the launch publishes the coefficients and dgamma / dbeta, bnfin.hpp BnBwdFin).
+// Only the combinations a launch can have are instantiated: V and bnpart go with the forward epilogue
+// (bst == nullptr) only, and V not with bpart; any other combination returns -3 and launches nothing.
 int psx_wino_fused(const float* x, const float* Uf, float* y, const float* res, float* stats, float* V, int N, int H,
                    int W, int C, int K, const WinoBwdStats* bst, const float* bnpart, const WinoBnFin* bnfin,
                    const float* sshift, const float* ybn, const float* bpart, const BnBwdFin* bbfin,
@@ -548,15 +607,33 @@ int psx_wino_fused(const float* x, const float* Uf, float* y, const float* res, 
   BnBwdFin bb{};
   if (bpart) bb = *bbfin;
   bb.det = (int)det_enabled();
-#define PSX_WF_ROW(G, R)                                                                                     \
-  {wino_fused_kernel<G, R, false, false, false>, wino_fused_kernel<G, R, true, false, false>,                 \
-   wino_fused_kernel<G, R, true, false, true>, wino_fused_kernel<G, R, true, true, false>,                    \
-   wino_fused_kernel<G, R, true, true, true>}
-  // [C / 16 == 8][res][variant]: forward, backward (ReLU mask from o / from the affine) x (one / two BN sums)
-  static const FK kF[2][2][5] = {{PSX_WF_ROW(4, false), PSX_WF_ROW(4, true)}, {PSX_WF_ROW(8, false), PSX_WF_ROW(8, true)}};
-#undef PSX_WF_ROW
-  const int var = bst ? 1 + 2 * (bs.mask_aff != nullptr) + (bs.y2 != nullptr) : 0;
-  hipLaunchKernelGGL(kF[C == 128][res != nullptr][var], dim3((unsigned)(rows * (K / kWfK))), dim3(512), 0, st, a, bf, bs, det, bb);
+  // Launch traits are template parameters; only the combinations a launch can have are instantiated.
+  // Forward [C / 16 == 8][res][input][V]: PLAIN / BNIN with or without V, BWDIN without.
+  // Data gradient [C / 16 == 8][res][variant][input]: (ReLU mask from o / from the affine) x (one /
+  // two BN sums), PLAIN / BWDIN, never V.
+#define PSX_WF_F(G, R, I, V) wino_fused_kernel<G, R, false, false, false, I, V>
+#define PSX_WF_FROW(G, R)                                                                        \
+  {{PSX_WF_F(G, R, kWfPlain, false), PSX_WF_F(G, R, kWfPlain, true)},                            \
+   {PSX_WF_F(G, R, kWfBnIn, false), PSX_WF_F(G, R, kWfBnIn, true)},                              \
+   {PSX_WF_F(G, R, kWfBwdIn, false), nullptr}}
+#define PSX_WF_B(G, R, M, T) {wino_fused_kernel<G, R, true, M, T, kWfPlain, false>, wino_fused_kernel<G, R, true, M, T, kWfBwdIn, false>}
+#define PSX_WF_BROW(G, R) {PSX_WF_B(G, R, false, false), PSX_WF_B(G, R, false, true), PSX_WF_B(G, R, true, false), PSX_WF_B(G, R, true, true)}
+  static const FK kFwd[2][2][3][2] = {{PSX_WF_FROW(4, false), PSX_WF_FROW(4, true)}, {PSX_WF_FROW(8, false), PSX_WF_FROW(8, true)}};
+  static const FK kBwd[2][2][4][2] = {{PSX_WF_BROW(4, false), PSX_WF_BROW(4, true)}, {PSX_WF_BROW(8, false), PSX_WF_BROW(8, true)}};
+#undef PSX_WF_F
+#undef PSX_WF_FROW
+#undef PSX_WF_B
+#undef PSX_WF_BROW
+  const int in = bpart ? kWfBwdIn : bnpart ? kWfBnIn : kWfPlain;
+  FK fk;
+  if (bst) {
+    if (in == kWfBnIn || V) return -3;  // not instantiated: the forward's traits
+    fk = kBwd[C == 128][res != nullptr][2 * (bs.mask_aff != nullptr) + (bs.y2 != nullptr)][in == kWfBwdIn];
+  } else {
+    fk = kFwd[C == 128][res != nullptr][in][V != nullptr];
+    if (!fk) return -3;
+  }
+  hipLaunchKernelGGL(fk, dim3((unsigned)(rows * (K / kWfK))), dim3(512), 0, st, a, bf, bs, det, bb);
   return (int)hipGetLastError();
 }
 

@@ -273,7 +273,8 @@ def wino_fused(x, uf, y, res, stats, v, nb, h, w, c, k, bst: "BwdStatsDesc | Non
     wino_wgrad. The other arguments as wino_conv. bwd_in = (y, part, BnBwdFin) (data gradient):
     x is dz of a BN whose backward apply is folded into the operand loads, dy = k1 dz + k2 y + k3
     from the slot sums ``part`` [STAT_SLOTS][2][c]; the launch writes the BnBwdFin's coefficients
-    and dgamma / dbeta."""
+    and dgamma / dbeta. ``v`` and ``bn_in`` go with the forward (``bst`` None) only and ``v`` not
+    with ``bwd_in``: other combinations are not instantiated and raise HipError (code -3)."""
     assert x.dtype == torch.float32 and y.dtype == torch.float32
     assert x.numel() == nb * h * w * c and y.numel() == nb * h * w * k and uf.numel() >= 40 * k * c
     assert v is None or v.numel() >= wino_v_floats(nb, h, w, c)
