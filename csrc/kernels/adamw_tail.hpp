@@ -21,16 +21,24 @@ struct AdamwScalars {
   float step_size, beta1, omb1, beta2, omb2, rsqrt_bc2, eps, decay;
 };
 
-// m, v: this element's moments, read and replaced. Returns p'.
-PSX_DEV float adamw_tail(float s, float pv, float& m, float& v, float gscale, const AdamwScalars& c) {
+// The moments and the step, shared with lamb_tail.hpp (the LAMB update forms the same m', v' and
+// quotient, so its moments are AdamW's bit for bit). m, v: this element's moments, read and
+// replaced. Returns m' / (sqrt(v') * rsqrt_bc2 + eps): sqrt, fma, divide.
+PSX_DEV float adamw_moments(float s, float& m, float& v, float gscale, const AdamwScalars& c) {
 #pragma clang fp contract(off)
   const float g = s * gscale;
   const float mn = __builtin_fmaf(c.beta1, m, c.omb1 * g);
   const float vn = __builtin_fmaf(c.beta2, v, c.omb2 * (g * g));
   const float den = __builtin_fmaf(__builtin_sqrtf(vn), c.rsqrt_bc2, c.eps);
-  const float upd = mn / den;
   m = mn;
   v = vn;
+  return mn / den;
+}
+
+// m, v: this element's moments, read and replaced. Returns p'.
+PSX_DEV float adamw_tail(float s, float pv, float& m, float& v, float gscale, const AdamwScalars& c) {
+#pragma clang fp contract(off)
+  const float upd = adamw_moments(s, m, v, gscale, c);
   return __builtin_fmaf(-c.step_size, upd, pv * c.decay);
 }
 

@@ -3,8 +3,8 @@
 // The SGD kernels (optim.hip, q8.hip) see the trainable prefix of the arena as one anonymous run
 // of floats. LARS scales every tensor's update by a trust ratio of two norms, so this file carries
 // the tensor boundaries of models/layout.py to the device (LarsSeg, one record per trainable
-// tensor) and reduces per tensor, in two launches over one flat grid of
-// (tensor, chunk of kLarsChunk elements) workgroups:
+// tensor; lars_seg.hpp, shared with lamb.hip) and reduces per tensor, in two launches over one
+// flat grid of (tensor, chunk of kLarsChunk elements) workgroups:
 //
 //   lars_norms : s = sum_k decode(g_k) in fp32 in source order k = 0..W-1 (exactly the sum of
 //                sgd_apply_multi), written as fp32 to the staging buffer; one {sum s^2, sum w^2}
@@ -28,75 +28,10 @@
 // the body is 8 elements per lane (one 16-byte fp16 load per source, two 16-byte fp32 accesses) when
 // every base pointer is 16-byte aligned, and the same 8 elements with scalar accesses otherwise.
 #include "common.hpp"
+#include "lars_seg.hpp"
 #include "sgd_tail.hpp"
 
 namespace psx {
-
-constexpr int kLarsChunk = 8192;  // elements per workgroup: 32 body elements per lane
-constexpr int kLarsMaxSrc = 32;   // reference server.py:424-426 caps the job at 32 workers
-
-struct LarsSeg {
-  long offset;      // first arena element of the tensor
-  long numel;
-  int adapt;        // 1: trust ratio + weight decay (ndim > 1); 0: lambda = 1, no weight decay
-  int first_block;  // first workgroup of the tensor in the flat grid
-};
-
-struct LarsSrcs {
-  const void* p[kLarsMaxSrc];
-  int n;
-};
-
-// which tensor owns this workgroup: every record's block range tested in parallel (-1: none)
-PSX_DEV int lars_find(const LarsSeg* __restrict__ table, int ntensors, int nblocks, int* sh) {
-  if (threadIdx.x == 0) *sh = -1;
-  __syncthreads();
-  const int bid = blockIdx.x;
-  for (int k = threadIdx.x; k < ntensors; k += blockDim.x) {
-    const int lo = table[k].first_block;
-    const int hi = k + 1 < ntensors ? table[k + 1].first_block : nblocks;
-    if (lo <= bid && bid < hi) *sh = k;
-  }
-  __syncthreads();
-  return *sh;
-}
-
-// arena range [a0, a1) of one chunk: scalar head [a0, ha), 8-element groups [ha, tb), tail [tb, a1)
-struct LarsRange {
-  long a0, ha, tb, a1;
-};
-PSX_DEV LarsRange lars_range(const LarsSeg& s, int chunk, long n) {
-  LarsRange r;
-  const long end = min(s.offset + s.numel, n);
-  r.a0 = min(s.offset + (long)chunk * kLarsChunk, end);
-  r.a1 = min(r.a0 + kLarsChunk, end);
-  r.ha = min(r.a1, (r.a0 + 7) & ~7L);
-  r.tb = r.ha + ((r.a1 - r.ha) & ~7L);
-  return r;
-}
-
-PSX_DEV float lars_ld(const uint16_t* g, long i) { return (float)__builtin_bit_cast(_Float16, g[i]); }
-PSX_DEV float lars_ld(const float* g, long i) { return g[i]; }
-
-PSX_DEV double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// block-wide {a, b} in double: wave trees, then the four waves in order (every thread gets both)
-PSX_DEV void lars_block_sum2(double& a, double& b, double (*red)[4]) {
-  a = wave_sum_f64(a);
-  b = wave_sum_f64(b);
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  if (l == 0) {
-    red[0][w] = a;
-    red[1][w] = b;
-  }
-  __syncthreads();
-  a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-  b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-}
 
 // GT: wire element (fp16 bits or fp32). DENSE: s is already in `stage` (no sources, no rewrite).
 // VEC: 16-byte accesses in the body (every base pointer 16-byte aligned).
@@ -141,27 +76,7 @@ __global__ __launch_bounds__(256) void lars_norms_kernel(const float* __restrict
           s[4 + j] = b[j];
         }
       } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s[j] = 0.f;
-        for (int k = 0; k < srcs.n; ++k) {
-          if constexpr (sizeof(GT) == 2) {
-            const u32x4 gv = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint16_t*>(srcs.p[k]) + i);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              s[2 * j] += (float)__builtin_bit_cast(_Float16, (uint16_t)(gv[j] & 0xffff));
-              s[2 * j + 1] += (float)__builtin_bit_cast(_Float16, (uint16_t)(gv[j] >> 16));
-            }
-          } else {
-            const float* g = reinterpret_cast<const float*>(srcs.p[k]) + i;
-            const f32x4 a = *reinterpret_cast<const f32x4*>(g);
-            const f32x4 b = *reinterpret_cast<const f32x4*>(g + 4);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              s[j] += a[j];
-              s[4 + j] += b[j];
-            }
-          }
-        }
+        lars_sum8<GT>(srcs, i, s);
         *reinterpret_cast<f32x4*>(stage + i) = (f32x4){s[0], s[1], s[2], s[3]};
         *reinterpret_cast<f32x4*>(stage + i + 4) = (f32x4){s[4], s[5], s[6], s[7]};
       }
@@ -204,14 +119,8 @@ __global__ __launch_bounds__(256) void lars_apply_kernel(float* __restrict__ p, 
   const int tid = threadIdx.x;
   float lam = 1.f, gs = gscale, wdl = 0.f;
   if (seg.adapt) {  // block-uniform
-    // the tensor's partials: partial j on lane (j - first) % 256, lane-serial, then the fixed trees
-    const long b0 = seg.first_block, b1 = b0 + (seg.numel + kLarsChunk - 1) / kLarsChunk;
-    double ss = 0.0, ww = 0.0;
-    for (long j = b0 + tid; j < b1; j += 256) {
-      ss += partials[2 * j];
-      ww += partials[2 * j + 1];
-    }
-    lars_block_sum2(ss, ww, red);
+    double ss, ww;  // the tensor's partials through the fixed trees (lars_seg.hpp)
+    lars_tensor_sum2(seg, partials, ss, ww, red);
     const double gn = (double)gscale * sqrt(ss), wn = sqrt(ww);
     if (wn > 0.0 && gn > 0.0) lam = (float)((double)trust * wn / (gn + (double)wd * wn + (double)eps));
     gs = lam * gscale;

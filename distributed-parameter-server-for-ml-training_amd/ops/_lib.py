@@ -109,6 +109,9 @@ _KERNEL_SIGS = {
     "psx_lars_apply": (i32, [vp, vp, vp, i64, vp, i32, i32, vp, vp, f32, f32, f32, f32, f32, f32, i32, vp, vp]),
     "psx_adamw_scalars": (i32, [f64, f64, f64, f64, f64, i64, vp]),
     "psx_adamw_apply_multi": (i32, [vp, vp, i32, i32, vp, vp, i64, f64, f32, f64, f64, f64, f64, i64, vp, vp]),
+    "psx_lamb_apply_multi": (i32, [vp, vp, i32, i32, vp, vp, vp, i64, vp, i32, i32, vp, vp, f32, f32, f32, f64, f64,
+                                   f64, i64, vp, vp]),
+    "psx_lamb_apply": (i32, [vp, vp, vp, vp, i64, vp, i32, i32, vp, vp, f32, f32, f32, f64, f64, f64, i64, vp, vp]),
     "psx_dc_apply": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, i32, i32, vp, vp]),
     "psx_dc_fetch_copy": (i32, [vp, vp, vp, i64, i64, vp]),
     "psx_guard_chunk": (i32, []),

@@ -607,15 +607,16 @@ def q8_decode(payload, dst, n=None, scale=1.0, add=False, off=0, cnt=None):
           "q8_decode")
 
 
-LARS_CHUNK = 8192  # kLarsChunk in csrc/kernels/lars.hip: elements per workgroup of the LARS grid
+LARS_CHUNK = 8192  # kLarsChunk in csrc/kernels/lars_seg.hpp: elements per workgroup of the LARS / LAMB grid
 _LARS_SEG = [("offset", "<i8"), ("numel", "<i8"), ("adapt", "<i4"), ("first_block", "<i4")]  # LarsSeg
 
 
 class LarsTable:
-    """The per-tensor segment table of the LARS update on the device (csrc/kernels/lars.hip
-    LarsSeg: one record per trainable tensor, in arena order) with the scratch the two launches
-    need: one {sum s^2, sum w^2} double pair per workgroup, and the float [ntensors] trust-ratio
-    table the apply fills (``ratios``; 1 for the tensors that are not adapted)."""
+    """The per-tensor segment table of the LARS and LAMB updates on the device
+    (csrc/kernels/lars_seg.hpp LarsSeg: one record per trainable tensor, in arena order) with the
+    scratch the two launches need: one double pair per workgroup ({sum s^2, sum w^2}; LAMB: {sum
+    u^2, sum w^2}), and the float [ntensors] ratio table the apply fills (``ratios``; 1 for the
+    tensors that are not adapted)."""
 
     def __init__(self, layout, device):
         import numpy as np
@@ -762,6 +763,62 @@ def adamw_apply(p, g, m, v, lr, t, gscale=1.0, beta1=0.9, beta2=0.999, eps=1e-8,
     """adamw_apply_multi with one source: a wire, or a gradient sum that is already dense fp32
     (decoded q8 / top-k payloads, an accumulated round)."""
     adamw_apply_multi(p, [g], m, v, lr, t, gscale=gscale, beta1=beta1, beta2=beta2, eps=eps, wd=wd, n=n, img=img)
+
+
+def lamb_scalars(t, beta1=0.9, beta2=0.999, eps=1e-8):
+    """The scalars of LAMB update number ``t``, in ADAMW_SCALARS order: adamw_scalars with lr = 1
+    and wd = 0, which is how csrc/kernels/lamb.hip derives them — ``step_size`` is the bias
+    correction 1 / (1 - beta1^t), ``decay`` is 1 and unused."""
+    return adamw_scalars(1.0, t, beta1=beta1, beta2=beta2, eps=eps, wd=0.0)
+
+
+def lamb_scalars_host(t, beta1=0.9, beta2=0.999, eps=1e-8):
+    """lamb_scalars without the kernel library (adamw_scalars_host)."""
+    return adamw_scalars_host(1.0, t, beta1=beta1, beta2=beta2, eps=eps, wd=0.0)
+
+
+def _lamb_common(p, stage, m, v, table, img, n, t, what):
+    n = _lars_common(p, stage, table, None, img, n, what)
+    assert int(t) >= 1, f"{what} t"
+    for x, nm in ((m, "m"), (v, "v")):
+        assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= n and x.device == p.device, \
+            f"{what} {nm}"
+    assert len({p.data_ptr(), stage.data_ptr(), m.data_ptr(), v.data_ptr()}) == 4, f"{what}: p, stage, m, v alias"
+    return n
+
+
+def lamb_apply_multi(p, srcs, stage, m, v, table: LarsTable, lr, t, gscale=1.0, wd=0.0, beta1=0.9, beta2=0.999,
+                     eps=1e-8, n=None, img=None):
+    """The LAMB server update, number ``t`` >= 1, from the W gathered wires (csrc/kernels/lamb.hip):
+    s = sum_k srcs[k] (fp32, list order, as sgd_apply_multi forms it), g = gscale * s, m = beta1*m +
+    (1-beta1)*g, v = beta2*v + (1-beta2)*g*g, r = m/(1-beta1^t) / (sqrt(v)/sqrt(1-beta2^t) + eps);
+    every tensor of ``table`` with ndim > 1 takes u = r + wd * p and p -= lr * (|p| / |u|) * u (ratio
+    1 when a norm is 0), the 1-D ones u = r and p -= lr * u. ``stage`` receives u, ``table.ratios``
+    the ratios, ``img`` (bf16) the image of the updated parameters. All sources fp16 or all fp32;
+    at most 32. Two launches on the current stream, no host synchronisation."""
+    n = _lamb_common(p, stage, m, v, table, img, n, t, "lamb_apply_multi")
+    assert 1 <= len(srcs) <= 32, "lamb_apply_multi sources"
+    fp16 = srcs[0].dtype == torch.float16
+    assert srcs[0].dtype in (torch.float16, torch.float32), "lamb_apply_multi"
+    state = {p.data_ptr(), stage.data_ptr(), m.data_ptr(), v.data_ptr()}
+    assert all(s.dtype == srcs[0].dtype and s.numel() >= n and s.device == p.device and s.is_contiguous()
+               and s.data_ptr() not in state for s in srcs), "lamb_apply_multi"
+    arr = (C.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
+    check(kernels().psx_lamb_apply_multi(ptr(p), arr, len(srcs), int(fp16), ptr(stage), ptr(m), ptr(v), n,
+                                         ptr(table.dev), table.ntensors, table.nblocks, ptr(table.partials),
+                                         ptr(table.ratios), float(lr), float(gscale), float(wd), float(beta1),
+                                         float(beta2), float(eps), int(t), ptr(img), stream_ptr()), "lamb_apply_multi")
+
+
+def lamb_apply(p, stage, m, v, table: LarsTable, lr, t, gscale=1.0, wd=0.0, beta1=0.9, beta2=0.999, eps=1e-8, n=None,
+               img=None):
+    """lamb_apply_multi for a gradient sum that is already dense fp32 in ``stage`` (decoded q8 /
+    top-k payloads, an accumulated round): ``stage`` is overwritten with u, then the same apply."""
+    n = _lamb_common(p, stage, m, v, table, img, n, t, "lamb_apply")
+    check(kernels().psx_lamb_apply(ptr(p), ptr(stage), ptr(m), ptr(v), n, ptr(table.dev), table.ntensors,
+                                   table.nblocks, ptr(table.partials), ptr(table.ratios), float(lr), float(gscale),
+                                   float(wd), float(beta1), float(beta2), float(eps), int(t), ptr(img), stream_ptr()),
+          "lamb_apply")
 
 
 def _dc_f32(t, n, dev, what):

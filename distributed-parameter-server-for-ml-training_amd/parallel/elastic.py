@@ -53,9 +53,9 @@ def enabled(cfg, transport, world: int) -> bool:
     return (getattr(cfg, "on_worker_loss", "restart") == "shrink" and cfg.mode == "sync"
             and (cfg.topology == "dedicated" or (cfg.topology == "colocated" and not cfg.overlap)) and world > 2 and getattr(transport, "native", False)
             and cfg.codec in ("fp16", "none", "topk") and not cfg.bn_sync
-            # _PyRollback snapshots the arena and the momentum buffer only: an AdamW job takes the
-            # restart-from-checkpoint path (the moments travel with the checkpoint)
-            and getattr(cfg, "optimizer", "sgd") != "adamw")
+            # _PyRollback snapshots the arena and the momentum buffer only: an AdamW or LAMB job takes
+            # the restart-from-checkpoint path (the moments travel with the checkpoint)
+            and getattr(cfg, "optimizer", "sgd") not in ("adamw", "lamb"))
 
 
 def lost_error(e: BaseException) -> bool:

@@ -52,8 +52,8 @@ def graph_round_enabled(cfg, transport) -> bool:
     return (os.environ.get("PSX_GRAPH_ROUND", "0") == "1" and getattr(transport, "native", False)
             and cfg.topology == "colocated" and not cfg.momentum and not cfg.bn_sync
             # per-bucket applies: a bucket may split a tensor (lars); a captured apply would bake the
-            # update number's scalars into the graph (adamw)
-            and cfg.optimizer == "sgd"
+            # update number's scalars into the graph (adamw, lamb), or its lr (--warmup-steps)
+            and cfg.optimizer == "sgd" and not cfg.warmup_steps > 0
             and not cfg.grad_guard)  # ... and no bucket sees the whole gradient's norm
 
 
@@ -64,6 +64,9 @@ class GraphRoundChannel(SyncCollectiveChannel):
     in_graph = True
 
     def __init__(self, transport, server, members, codec, wire, buckets, device):
+        if server is not None and getattr(server.cfg, "warmup_steps", 0) > 0:
+            raise ValueError("the captured graph round holds a fixed lr: --warmup-steps runs on the serial or the "
+                             "bucketed round")
         super().__init__(transport, server, members, codec, wire=wire)
         assert wire is not None, "every rank of the graph round trains (colocated topology)"
         self.buckets = buckets

@@ -77,11 +77,12 @@ def _lib():
 
 def native_loop_enabled(cfg, transport) -> bool:
     """Default for async jobs on the native transport (PSX_NATIVE_LOOP=0: the Python loop). The
-    C++ loop launches the SGD kernels itself: --optimizer lars / adamw and the gradient guard
-    (--clip-norm / --skip-nonfinite) are served by the Python loop."""
+    C++ loop launches the SGD kernels itself, with the lr it was started with: --optimizer lars /
+    adamw / lamb, the gradient guard (--clip-norm / --skip-nonfinite) and --warmup-steps are
+    served by the Python loop."""
     return (os.environ.get("PSX_NATIVE_LOOP", "1") == "1" and getattr(transport, "native", False)
             and cfg.codec in ("fp16", "none") and not cfg.bn_sync and cfg.optimizer == "sgd"
-            and not cfg.grad_guard)
+            and not cfg.grad_guard and not cfg.warmup_steps > 0)
 
 
 class NativeServerLoop:
@@ -103,6 +104,8 @@ class NativeServerLoop:
         if cfg.grad_guard:
             raise ValueError("the native event loop applies plain SGD: --clip-norm / --skip-nonfinite run on the "
                              "Python server loop")
+        if cfg.warmup_steps > 0:
+            raise ValueError("the native event loop holds a fixed lr: --warmup-steps runs on the Python server loop")
         self.small_idx = small_index_of(lay).to(server.device)
         max_wid = max([expected] + [w + 1 for w in rank_of_wid])
         self.max_wid = max_wid

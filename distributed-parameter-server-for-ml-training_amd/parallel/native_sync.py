@@ -106,7 +106,8 @@ def native_sync_enabled(cfg, transport, chan, server, rank: int) -> bool:
     if not (os.environ.get("PSX_NATIVE_SYNC", "1") == "1" and rank == 0 and server is not None
             and getattr(transport, "native", False) and getattr(transport, "world_size", 1) > 1
             and cfg.mode == "sync" and cfg.topology == "dedicated" and cfg.codec in ("fp16", "none")
-            and cfg.optimizer == "sgd"  # the C++ rounds launch the SGD kernels: LARS / AdamW stay in Python
+            and cfg.optimizer == "sgd"  # the C++ rounds launch the SGD kernels: LARS / AdamW / LAMB stay in Python
+            and not cfg.warmup_steps > 0  # ... with the lr they were started with
             and not cfg.bn_sync and type(chan) in (SyncCollectiveChannel, OverlapSyncChannel)
             and not getattr(chan, "root_worker", True) and getattr(chan, "agg_mode", "gather") == "gather"):
         return False
@@ -127,6 +128,8 @@ class NativeSyncServer:
         if cfg.optimizer != "sgd":  # csrc/server/sync_loop.cpp launches psx_sgd_apply_multi itself
             raise ValueError(f"the native sync rounds apply plain SGD: --optimizer {cfg.optimizer} runs on the Python "
                              f"server")
+        if cfg.warmup_steps > 0:
+            raise ValueError("the native sync rounds hold a fixed lr: --warmup-steps runs on the Python server")
         self.server, self.t, self.chan = server, transport, chan
         self.gs0 = server.core.global_step  # the core's step when this loop took over
         dev = server.device

@@ -148,6 +148,9 @@ def run_local_threads(cfg, steps: int, log=print, emit: bool = True) -> dict:
     if cfg.grad_guard:
         raise ValueError("run_local_threads is bound to the native event loop, which applies plain SGD: "
                          "--clip-norm / --skip-nonfinite are not available here")
+    if cfg.warmup_steps > 0:
+        raise ValueError("run_local_threads is bound to the native event loop, which holds a fixed lr: "
+                         "--warmup-steps is not available here")
     cfg.resolve_overlap(1)
     device = _device_for(0)
     W = cfg.workers
@@ -258,7 +261,8 @@ def _interleave(cfg, workers, server, log, depart=None):
                     wk.fetch_parameters()
             if cfg.verbose and b % 50 == 0:
                 log(f"  epoch {epoch + 1} batch {b}/{steps} loss(w0) {workers[0].compute.last_loss():.4f} "
-                    f"global_step {server.core.global_step}")
+                    f"global_step {server.core.global_step}"
+                    + (f" lr {server.lr:.6g}" if cfg.warmup_steps > 0 else ""))
             if cfg.max_steps and max(wk.local_step_counter for wk in workers) >= cfg.max_steps:
                 break
         if server.device.type == "cuda":

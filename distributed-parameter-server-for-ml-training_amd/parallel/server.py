@@ -55,7 +55,7 @@ class ParameterServer:
         self.layout = layout
         self.device = torch.device(device)
         self.total_workers = total_workers if total_workers is not None else cfg.workers
-        self.lr = cfg.lr
+        self.lr = cfg.lr  # the configured base; reads give the open update's effective value (lr property)
         self.log = log if cfg.verbose else (lambda *a, **k: None)
         self.arena = init_arena.to(self.device, dtype=torch.float32).contiguous()
         self.counters = counters if counters is not None else torch.zeros(max(1, layout.num_counters), dtype=torch.int64)
@@ -81,7 +81,18 @@ class ParameterServer:
         self._adamw = cfg.optimizer == "adamw"
         self.adam_m = self.adam_v = None
         self.adam_t = 0
-        if self._adamw:
+        # --optimizer lamb: the AdamW moments under the LARS table; every whole-arena update goes
+        # through _lamb_update (the pair of csrc/kernels/lamb.hip, staged through agg)
+        self._lamb = cfg.optimizer == "lamb"
+        self._lamb_ratios = None   # CPU arena: the last update's ratios of the adapted tensors
+        self._lamb_applied = False
+        if self._lamb:
+            self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+            if self.device.type == "cuda":
+                from ..ops import kernels as K
+
+                self._lars_tab = K.lars_table(layout, self.device)
+        if self._adamw or self._lamb:
             self.adam_m = torch.zeros_like(self.params)
             self.adam_v = torch.zeros_like(self.params)
         # --clip-norm / --skip-nonfinite: every whole-arena update goes through _guard_update (the
@@ -124,6 +135,21 @@ class ParameterServer:
         if cfg.resume:
             self.resume(cfg.resume)
 
+    # ------------------------------------------------------------------ learning rate (--warmup-steps)
+    @property
+    def lr(self) -> float:
+        """The learning rate of the open update, number k = completed updates + 1 (the count
+        finish_round_apply advances and resume restores): lr * min(1, k / warmup_steps), in
+        double; the configured lr with --warmup-steps 0. Every update path reads it at call time."""
+        n = int(getattr(self.cfg, "warmup_steps", 0) or 0)
+        if n <= 0:
+            return self._base_lr
+        return self._base_lr * min(1.0, (self.core.global_step + 1) / n)
+
+    @lr.setter
+    def lr(self, value: float):
+        self._base_lr = float(value)
+
     # ------------------------------------------------------------------ numerics
     def apply(self, grads: torch.Tensor, weight: float, worker_id: int | None = None):
         """p <- p - lr * (weight * g [+ wd p]) [momentum]; grads are fp16 wire, fp32, or a top-k
@@ -136,7 +162,7 @@ class ParameterServer:
             return self.finish_round_apply(self._time_end(t0))
         if grads.dtype == torch.int32:  # top-k payload (parallel/topk.py)
             if not self.cfg.momentum and not self.cfg.weight_decay and not self._lars and not self._guard \
-                    and not self._adamw:
+                    and not self._adamw and not self._lamb:
                 # no optimizer state: scatter straight into the fp32 master parameters
                 topk.decode_add(grads, self.params, -self.lr * weight, self._kcap)
                 self._wire_stale = True  # the bf16 image was not written by this update
@@ -153,8 +179,9 @@ class ParameterServer:
         launch on the device (the weight image, when enabled, written in the same pass); the
         torch decode into the aggregation buffer on a CPU arena. LARS: decoded into the
         aggregation buffer on either, then the dense entry of the LARS pair; the gradient guard
-        likewise (its dense entry), and AdamW (the one-source fp32 form of its kernel)."""
-        if self.device.type == "cuda" and not self._lars and not self._guard and not self._adamw:
+        likewise (its dense entry), AdamW (the one-source fp32 form of its kernel) and LAMB (its
+        dense entry)."""
+        if self.device.type == "cuda" and not self._lars and not self._guard and not self._adamw and not self._lamb:
             from ..ops import kernels as K
 
             img = self.wire.img[: self.n] if self.wire is not None else None
@@ -294,6 +321,9 @@ class ParameterServer:
         if self._lars:
             self._lars_whole(lo, hi)
             return self._lars_update([g], weight)
+        if self._lamb:
+            self._lamb_whole(lo, hi)
+            return self._lamb_update([g], weight)
         if self._guard:
             self._guard_whole(lo, hi)
             return self._guard_update([g], weight)
@@ -331,6 +361,9 @@ class ParameterServer:
         if self._lars:
             self._lars_whole(lo, hi)
             return self._lars_update(list(srcs), weight)
+        if self._lamb:
+            self._lamb_whole(lo, hi)
+            return self._lamb_update(list(srcs), weight)
         if self._guard:
             self._guard_whole(lo, hi)
             return self._guard_update(list(srcs), weight)
@@ -463,6 +496,83 @@ class ParameterServer:
             return None
         return {"min": float(r.min()), "median": float(r.median()), "max": float(r.max())}
 
+    # ------------------------------------------------------------------ LAMB (--optimizer lamb)
+    def _lamb_whole(self, lo: int, hi: int):
+        if (lo, hi) != (0, self.n):
+            raise ValueError(f"--optimizer lamb needs every tensor's norm before its first element moves: a partial "
+                             f"range [{lo}, {hi}) of {self.n} cannot be applied (no bucketed or sharded updates)")
+
+    def _lamb_update(self, srcs: list, weight: float):
+        """The whole-arena LAMB update (You et al. 2020), number adam_t + 1, from dense wires (fp16
+        / fp32, summed in fp32 in list order) or from the aggregation buffer itself (a decoded or
+        accumulated sum): g = weight * s; m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g g;
+        r = m / (1 - beta1^t) / (sqrt(v) / sqrt(1 - beta2^t) + eps); tensors with ndim > 1: u = r +
+        wd * w, phi = |w| / |u| (1 when a norm is 0); 1-D tensors: u = r, phi = 1; w -= lr * phi * u.
+        No clamp on |w|, no global gradient normalisation. Device: the two launches of
+        csrc/kernels/lamb.hip (the aggregation buffer ends holding u); CPU arena: the same formula
+        in torch from the same fp32 scalars, tensor by tensor (equal to a tolerance, not bit for
+        bit: the reduction orders differ)."""
+        import numpy as np
+
+        from ..ops import kernels as K
+
+        cfg = self.cfg
+        self._lamb_applied = True
+        t = self.adam_t + 1
+        hp = dict(beta1=cfg.adam_beta1, beta2=cfg.adam_beta2, eps=cfg.adam_eps)
+        staged = len(srcs) == 1 and srcs[0].dtype == torch.float32 and srcs[0].data_ptr() == self.agg.data_ptr()
+        if self.device.type == "cuda":
+            kw = dict(lr=self.lr, t=t, gscale=weight, wd=cfg.weight_decay, n=self.n,
+                      img=self.wire.img[: self.n] if self.wire is not None else None, **hp)
+            if staged:
+                K.lamb_apply(self.params, self.agg, self.adam_m, self.adam_v, self._lars_tab, **kw)
+            else:
+                K.lamb_apply_multi(self.params, [s[: self.n] for s in srcs], self.agg, self.adam_m, self.adam_v,
+                                   self._lars_tab, **kw)
+            return
+        if not staged:
+            self.agg.zero_()
+            for s in srcs:  # fixed order, fp32 accumulation
+                self.agg.add_(s[: self.n].to(torch.float32))
+        if self.wire is not None:
+            self._wire_stale = True
+        try:
+            bc1, b1, omb1, b2, omb2, rbc2, eps, _ = K.lamb_scalars(t, **hp)
+        except (OSError, RuntimeError, AttributeError):  # the kernel library is not loaded here
+            bc1, b1, omb1, b2, omb2, rbc2, eps, _ = K.lamb_scalars_host(t, **hp)
+        lr, wd = float(np.float32(self.lr)), float(np.float32(cfg.weight_decay))
+        g = self.agg * float(np.float32(weight))
+        self.adam_m.copy_(self.adam_m * b1 + g * omb1)
+        self.adam_v.copy_(self.adam_v * b2 + (g * g) * omb2)
+        r = (self.adam_m / (self.adam_v.sqrt() * rbc2 + eps)) * bc1
+        ratios = []
+        for e in self.layout.entries.values():
+            if e.region != "param" or not e.numel:
+                continue
+            w = self.params[e.offset:e.offset + e.numel]
+            u = r[e.offset:e.offset + e.numel]
+            phi = 1.0
+            if len(e.shape) > 1:
+                u = u + wd * w
+                wn, un = float(w.double().norm()), float(u.double().norm())
+                phi = float(np.float32(wn / un)) if wn > 0 and un > 0 else 1.0
+                ratios.append(phi)
+            w.sub_(float(np.float32(lr * phi)) * u)
+        self._lamb_ratios = ratios
+
+    def lamb_trust_ratios(self):
+        """{min, median, max} of the last update's ratios |w| / |u| over the adapted tensors (read
+        from the device ratio table here, not per round); None before the first update."""
+        if not self._lamb_applied:
+            return None
+        if self._lars_tab is not None:
+            r = self._lars_tab.ratios.cpu()[torch.tensor(self._lars_tab.adapt)]
+        else:
+            r = torch.tensor(self._lamb_ratios)
+        if not r.numel():
+            return None
+        return {"min": float(r.min()), "median": float(r.median()), "max": float(r.max())}
+
     # ------------------------------------------------------------------ gradient guard (--clip-norm, --skip-nonfinite)
     def _guard_whole(self, lo: int, hi: int):
         if (lo, hi) != (0, self.n):
@@ -539,7 +649,7 @@ class ParameterServer:
         """Closes one update (global_step + 1). ``dt`` >= 0: its host-measured time (CPU arena);
         else the device ranges timed since the last close (deferred), or none (graph capture)."""
         self._mom_first = False
-        if self._adamw:
+        if self._adamw or self._lamb:
             self.adam_t += 1
         if self._round_ev:
             self._ev_pending = self._ev_pending + [self._round_ev]
@@ -732,6 +842,8 @@ class ParameterServer:
         t0 = self._time_begin()
         if self._lars:
             self._lars_update(list(srcs), res.weight)
+        elif self._lamb:
+            self._lamb_update(list(srcs), res.weight)
         elif self._guard:
             self._guard_update(list(srcs), res.weight)
         elif self._adamw:
@@ -795,9 +907,9 @@ class ParameterServer:
     def checkpoint(self, path: str | None = None) -> str:
         step = self.core.global_step
         path = path or ckpt.path_for(self.cfg.ckpt_dir, step)
-        ckpt.save(path, self.layout, self.arena, self.counters, step, self.cfg.mode, self.total_workers, self.lr,
-                  self.momentum_buf, self.cfg.to_json(), dc_meansquare=self._dc_ms,
-                  adam=(self.adam_m, self.adam_v, self.adam_t) if self._adamw else None)
+        ckpt.save(path, self.layout, self.arena, self.counters, step, self.cfg.mode, self.total_workers,
+                  self._base_lr, self.momentum_buf, self.cfg.to_json(), dc_meansquare=self._dc_ms,
+                  adam=(self.adam_m, self.adam_v, self.adam_t) if self._adamw or self._lamb else None)
         self.log(f"[Checkpoint] global step {step} -> {path}")
         return path
 
@@ -826,9 +938,9 @@ class ParameterServer:
         ms = obj.get("server_optimizer_state", {}).get("dc_meansquare")
         if ms is not None and self._dc_ms is not None:
             self._dc_ms.copy_(ms.to(self.device))
-        # AdamW: both moments and the update count (absent, e.g. an SGD server's checkpoint: zero
-        # moments, the next update is t = 1)
-        if self._adamw:
+        # AdamW / LAMB: both moments and the update count (absent, e.g. an SGD server's checkpoint:
+        # zero moments, the next update is t = 1)
+        if self._adamw or self._lamb:
             st = obj.get("server_optimizer_state", {})
             if st.get("adam_m") is not None and st.get("adam_v") is not None:
                 self.adam_m.copy_(st["adam_m"].to(self.device))
@@ -852,6 +964,13 @@ class ParameterServer:
         if self._adamw:
             m["adamw"] = {"beta1": float(self.cfg.adam_beta1), "beta2": float(self.cfg.adam_beta2),
                           "eps": float(self.cfg.adam_eps), "steps": int(self.adam_t)}
+        if self._lamb:
+            m["lamb"] = {"beta1": float(self.cfg.adam_beta1), "beta2": float(self.cfg.adam_beta2),
+                         "eps": float(self.cfg.adam_eps), "steps": int(self.adam_t)}
+            m["lamb_trust_ratio"] = self.lamb_trust_ratios()
+        if int(getattr(self.cfg, "warmup_steps", 0) or 0) > 0:
+            m["warmup_steps"] = int(self.cfg.warmup_steps)
+            m["effective_lr"] = float(self.lr)
         if self._guard:
             m["gradient_guard"] = self.guard_counters()
         if self._dc:

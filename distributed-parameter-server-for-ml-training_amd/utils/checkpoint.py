@@ -9,7 +9,7 @@ de-facto wire layout is the FetchReply payload ``{state_dict_name: ndarray}``
      "global_step": int, "mode": str, "total_workers": int, "lr": float,
      "server_optimizer_state": {"momentum": tensor | None,
                                 "dc_meansquare": tensor   # optional: --dc-adaptive mean square
-                                "adam_m", "adam_v": tensor, "adam_step": int   # optional: --optimizer adamw
+                                "adam_m", "adam_v": tensor, "adam_step": int   # optional: --optimizer adamw / lamb
                                 }, "config": json str}
 
 Written with torch.save to a temp file + atomic rename; loaded with

@@ -11,7 +11,8 @@ Keeps every flag and environment variable of the reference with the same default
 
 and adds the MI355X-native knobs: --gpus/--nproc, --codec, --topk-ratio,
 --dtype, --momentum/--weight-decay (server optimizer, default 0 = reference parity),
---optimizer {sgd,lars,adamw} with --lars-trust/--lars-eps and --adam-beta1/--adam-beta2/--adam-eps,
+--optimizer {sgd,lars,adamw,lamb} with --lars-trust/--lars-eps and --adam-beta1/--adam-beta2/--adam-eps,
+--warmup-steps (linear lr warmup of the server update),
 --dc-lambda/--dc-adaptive (async delay compensation), --clip-norm/--skip-nonfinite (global-norm clipping, non-finite guard), --model,
 --synthetic, --ckpt-every/--resume, --sync-semantics {barrier,reference}, --topology.
 Precedence: explicit CLI flag > JSON config file (--config) > environment > default.
@@ -74,6 +75,14 @@ class PSConfig:
     adam_beta1: float = 0.9
     adam_beta2: float = 0.999
     adam_eps: float = 1e-8
+    # lamb (csrc/kernels/lamb.hip, You et al. 2020): the adamw moments (adam_beta1 / adam_beta2 /
+    # adam_eps) with a per-tensor ratio |w| / |u| on the update u = mhat / (sqrt(vhat) + adam_eps) +
+    # wd w of every tensor with ndim > 1; 1-D tensors take ratio 1 and no weight decay (the lars
+    # convention). No clamp on |w|, no global gradient normalisation. Scope as lars: the Python
+    # server's whole-arena updates only; momentum must be 0.
+    # warmup_steps N > 0: update number k (1-based) runs with lr * min(1, k / N); 0 = constant lr.
+    # Python server only: the native loops and the graph round hold a fixed lr.
+    warmup_steps: int = 0
     # async delay compensation (DC-ASGD, csrc/kernels/dcasgd.hip): the server keeps the parameters
     # each worker last fetched (bak) and applies g + lam * g * g * (w - bak) in place of g.
     # dc_lambda 0 = off; dc_adaptive: lam = dc_lambda / sqrt(ms + dc_eps) with ms the running mean
@@ -147,8 +156,8 @@ class PSConfig:
             raise ValueError(f"--codec must be none, fp16, q8 or topk, got {self.codec!r}")
         if self.topology not in ("colocated", "dedicated", "sharded"):
             raise ValueError(f"--topology must be colocated, dedicated or sharded, got {self.topology!r}")
-        if self.optimizer not in ("sgd", "lars", "adamw"):
-            raise ValueError(f"--optimizer must be sgd, lars or adamw, got {self.optimizer!r}")
+        if self.optimizer not in ("sgd", "lars", "adamw", "lamb"):
+            raise ValueError(f"--optimizer must be sgd, lars, adamw or lamb, got {self.optimizer!r}")
         if self.optimizer == "adamw":
             if not (0.0 <= self.adam_beta1 < 1.0) or not (0.0 <= self.adam_beta2 < 1.0):
                 raise ValueError("--optimizer adamw: --adam-beta1 and --adam-beta2 must be in [0, 1)")
@@ -156,6 +165,19 @@ class PSConfig:
                 raise ValueError("--optimizer adamw: --adam-eps must be > 0")
             if self.momentum:
                 raise ValueError("--optimizer adamw: --adam-beta1 is the momentum, --momentum must be 0")
+        if self.optimizer == "lamb":
+            if not (0.0 <= self.adam_beta1 < 1.0) or not (0.0 <= self.adam_beta2 < 1.0):
+                raise ValueError("--optimizer lamb: --adam-beta1 and --adam-beta2 must be in [0, 1)")
+            if not self.adam_eps > 0.0:
+                raise ValueError("--optimizer lamb: --adam-eps must be > 0")
+            if self.momentum:
+                raise ValueError("--optimizer lamb: --adam-beta1 is the momentum, --momentum must be 0")
+            if self.topology == "sharded":  # a shard boundary may split a tensor
+                raise ValueError("--optimizer lamb needs whole tensors on one server: not with --topology sharded")
+            if self.overlap is True:  # a gradient bucket may split a tensor
+                raise ValueError("--optimizer lamb updates the whole arena at once: not with --overlap")
+        if int(self.warmup_steps) < 0:
+            raise ValueError("--warmup-steps must be >= 0")
         if self.optimizer == "lars":
             if not (self.lars_trust > 0.0) or self.lars_eps < 0.0:
                 raise ValueError("--optimizer lars: --lars-trust must be > 0 and --lars-eps >= 0")
@@ -228,13 +250,13 @@ class PSConfig:
         """--overlap / --no-overlap, or auto: bucketed rounds when there are peers to exchange
         with and the round qualifies (sync, one push per batch, dense wire, rank-0 server). The
         error-feedback codecs (q8, topk) encode the whole gradient at once, and --optimizer lars
-        and the gradient guard (--clip-norm / --skip-nonfinite) need a norm of the whole gradient
+        / lamb and the gradient guard (--clip-norm / --skip-nonfinite) need a norm of the whole gradient
         before the first element moves: no bucketed rounds. --optimizer adamw is element-wise and
         stays eligible."""
         if self.overlap is None:
             self.overlap = (world > 1 and self.mode == "sync" and max(1, self.sync_steps) == 1
-                            and self.dense_wire and self.topology != "sharded" and self.optimizer != "lars"
-                            and not self.grad_guard)
+                            and self.dense_wire and self.topology != "sharded"
+                            and self.optimizer not in ("lars", "lamb") and not self.grad_guard)
         return bool(self.overlap)
 
     @property
@@ -277,15 +299,20 @@ def add_arguments(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
       help="worker compute precision: fp32 (reference, default) or bf16 (fast path)")
     A("--momentum", type=float, default=None)
     A("--weight-decay", type=float, default=None)
-    A("--optimizer", choices=["sgd", "lars", "adamw"], default=None,
+    A("--optimizer", choices=["sgd", "lars", "adamw", "lamb"], default=None,
       help="server optimizer: sgd (default), lars (layer-wise trust ratio on tensors with ndim > 1; "
-           "uses --momentum / --weight-decay; Python server, whole-arena updates) or adamw (Adam with "
-           "decoupled --weight-decay; Python server, also bucketed and sharded rounds)")
+           "uses --momentum / --weight-decay; Python server, whole-arena updates), adamw (Adam with "
+           "decoupled --weight-decay; Python server, also bucketed and sharded rounds) or lamb (the Adam "
+           "moments with a per-tensor ratio |w| / |update| on tensors with ndim > 1; Python server, "
+           "whole-arena updates)")
     A("--lars-trust", type=float, default=None, help="LARS trust coefficient (default 0.001)")
     A("--lars-eps", type=float, default=None, help="LARS denominator epsilon (default 1e-8)")
-    A("--adam-beta1", type=float, default=None, help="AdamW first-moment decay (default 0.9)")
-    A("--adam-beta2", type=float, default=None, help="AdamW second-moment decay (default 0.999)")
-    A("--adam-eps", type=float, default=None, help="AdamW denominator epsilon (default 1e-8)")
+    A("--adam-beta1", type=float, default=None, help="AdamW / LAMB first-moment decay (default 0.9)")
+    A("--adam-beta2", type=float, default=None, help="AdamW / LAMB second-moment decay (default 0.999)")
+    A("--adam-eps", type=float, default=None, help="AdamW / LAMB denominator epsilon (default 1e-8)")
+    A("--warmup-steps", type=int, default=None,
+      help="linear warmup of the server learning rate: update k (1-based) runs with lr * min(1, k / N); "
+           "0 = off (default); Python server only")
     A("--dc-lambda", type=float, default=None,
       help="async delay compensation (DC-ASGD): apply g + lambda*g*g*(w - w_at_fetch); 0 = off (default)")
     A("--dc-adaptive", action="store_true", default=None,

@@ -21,6 +21,12 @@
 * ``psx_fp32_adamw``  psx_fp32 with the AdamW server optimizer (--optimizer adamw, lr 1e-3, weight decay
                       1e-2, fp16 wire), its own run: recorded next to ``psx_fp32`` and compared with
                       it (``adamw_vs_psx_fp32``), not a parity claim and not asserted.
+* ``psx_fp32_lamb``   psx_fp32 with the LAMB server optimizer (--optimizer lamb, lr ``--lamb-lr``, default
+                      0.01, weight decay 1e-2, fp16 wire), its own run like the AdamW curve: compared
+                      with ``psx_fp32`` (``lamb_vs_psx_fp32``), not a parity claim and not asserted.
+* ``psx_fp32_lars_warmup`` ``psx_fp32_lars`` with a linear lr warmup over ``--warmup-steps`` updates
+                      (default 50): whether the warmup closes the LARS curve's gap to plain SGD
+                      (``lars_warmup_vs_psx_fp32``).
 * ``psx_bf16``        the bf16 HIP engine (fast path), fp16 wire, bf16conv fetch.
 * ``psx_fp32_reference_bn`` psx_fp32 with the reference's BN semantics (no --bn-sync): same
                       training curve, but the evaluation runs on never-learned running statistics.
@@ -203,6 +209,8 @@ def main():
     ap.add_argument("--out", default="gpurun_out/convergence")
     ap.add_argument("--skip-w4", action="store_true")
     ap.add_argument("--lars-lr", type=float, default=2.0, help="lr of the psx_fp32_lars curve")
+    ap.add_argument("--lamb-lr", type=float, default=0.01, help="lr of the psx_fp32_lamb curve")
+    ap.add_argument("--warmup-steps", type=int, default=50, help="warmup of the psx_fp32_lars_warmup curve")
     ap.add_argument("--only", default="", help="comma-separated subset of the curves to run (default: all)")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
@@ -211,6 +219,8 @@ def main():
     runs = {}
     lars = dict(optimizer="lars", lr=args.lars_lr, momentum=0.9, weight_decay=5e-4)
     adamw = dict(optimizer="adamw", lr=1e-3, weight_decay=1e-2)
+    lamb = dict(optimizer="lamb", lr=args.lamb_lr, weight_decay=1e-2)
+    lars_wu = dict(lars, warmup_steps=args.warmup_steps)
     only = [x for x in args.only.split(",") if x]
     for name, fn in (("torch_fp32", lambda: run_torch(args, train, test, 0)),
                      ("torch_fp32_init1", lambda: run_torch(args, train, test, 1)),
@@ -219,6 +229,8 @@ def main():
                      ("psx_fp32_q8", lambda: run_psx(args, train, test, "fp32", "q8")),
                      ("psx_fp32_lars", lambda: run_psx(args, train, test, "fp32", "fp16", **lars)),
                      ("psx_fp32_adamw", lambda: run_psx(args, train, test, "fp32", "fp16", **adamw)),
+                     ("psx_fp32_lamb", lambda: run_psx(args, train, test, "fp32", "fp16", **lamb)),
+                     ("psx_fp32_lars_warmup", lambda: run_psx(args, train, test, "fp32", "fp16", **lars_wu)),
                      ("psx_bf16", lambda: run_psx(args, train, test, "bf16", "fp16")),
                      ("psx_fp32_reference_bn", lambda: run_psx(args, train, test, "fp32", "fp16", bn_sync=False))):
         if only and name not in only and name != "torch_fp32":
@@ -239,7 +251,7 @@ def main():
                      "test_acc_diff_pp": r["test_acc"] - runs["torch_fp32"]["test_acc"]}
         print(f"  vs torch_fp32: {name:18s} {json.dumps(cmp[name])}", flush=True)
     vs_psx = {}
-    for name in ("psx_fp32_q8", "psx_fp32_lars", "psx_fp32_adamw"):
+    for name in ("psx_fp32_q8", "psx_fp32_lars", "psx_fp32_adamw", "psx_fp32_lamb", "psx_fp32_lars_warmup"):
         if name not in runs or "psx_fp32" not in runs:
             continue
         d = smooth(runs[name]["loss"], args.window) - smooth(runs["psx_fp32"]["loss"], args.window)
@@ -259,6 +271,8 @@ def main():
                                           "20% label noise, 100 classes",
            "runs": runs, "vs_torch_fp32": cmp, "q8_vs_psx_fp32": vs_psx.get("psx_fp32_q8"),
            "lars_vs_psx_fp32": vs_psx.get("psx_fp32_lars"), "adamw_vs_psx_fp32": vs_psx.get("psx_fp32_adamw"),
+           "lamb_vs_psx_fp32": vs_psx.get("psx_fp32_lamb"),
+           "lars_warmup_vs_psx_fp32": vs_psx.get("psx_fp32_lars_warmup"),
            "w4_sync": w4}
     with open(os.path.join(args.out, "convergence_parity.json"), "w") as f:
         json.dump(out, f)
