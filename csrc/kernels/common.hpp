@@ -71,6 +71,9 @@ PSX_DEV float bf2f(uint16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 // fp32 -> bf16, round to nearest even: gfx950's v_cvt_pk_bf16_f32 (one instruction per pair; the
 // integer-arithmetic rounding it replaces was ~7 VALU per value, a third of the bf16 conv epilogue)
 // (A/B builds: -D PSX_SW_BF16 keeps the integer version)
+// Both forms below (single and packed) agree with each other and with torch.bfloat16 on ties of
+// either parity, on overflow to inf and on fp32 subnormals, which are rounded like any other value
+// and not flushed (tests/test_sgd_gpu.py::test_image_rounding_edges).
 typedef __bf16 psx_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float psx_f32x2 __attribute__((ext_vector_type(2)));
 #ifdef PSX_SW_BF16

@@ -18,6 +18,16 @@ namespace psx {
 PSX_DEV float ld_grad(const uint16_t* g, size_t i) { return (float)__builtin_bit_cast(_Float16, g[i]); }
 PSX_DEV float ld_grad(const float* g, size_t i) { return g[i]; }
 
+// fp16 bits of an fp32 value, round to nearest even. The empty asm makes t a value of its own:
+// without it the compiler folds the fp32 multiply that produced t into v_fma_mixlo_f16, which
+// rounds the exact product once (on the MI355X that differs from the codec's definition,
+// (g * scale).half(), where the fp32 product falls on an fp16 tie) and, adding +0, turns a -0
+// product into +0.
+PSX_DEV uint16_t f2h(float t) {
+  __asm__ volatile("" : "+v"(t));
+  return __builtin_bit_cast(uint16_t, (_Float16)t);
+}
+
 // img (optional): bf16 image of the updated parameters, written in the same pass — the fetch
 // wire / the workers' conv-operand source (parallel/codec.py), so no separate pack kernel.
 template <typename GT, bool MOM>
@@ -33,15 +43,16 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
   }
 }
 
-// vectorised fp16-gradient fast path (no momentum): 8 elements per lane
+// vectorised fp16-gradient fast path (no momentum): 8 elements per lane, every element through
+// sgd_tail like the scalar kernel, so a slice's alignment does not change the bits of its update
 template <bool IMG>
 __global__ __launch_bounds__(256) void sgd_apply_h8_kernel(float* __restrict__ p, const uint16_t* __restrict__ g,
-                                                           size_t n, float step, float wd_step,
+                                                           size_t n, float lr, float gscale, float wd,
                                                            uint16_t* __restrict__ img) {
   const size_t n8 = n >> 3;
   if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {  // tail (n % 8 elements)
     const size_t i = (n8 << 3) + threadIdx.x;
-    const float nv = p[i] - (step * (float)__builtin_bit_cast(_Float16, g[i]) + wd_step * p[i]);
+    const float nv = sgd_tail<false>(ld_grad(g, i), p[i], nullptr, lr, gscale, 0.f, wd, 0);
     p[i] = nv;
     if (IMG) img[i] = f2bf(nv);
   }
@@ -56,10 +67,10 @@ __global__ __launch_bounds__(256) void sgd_apply_h8_kernel(float* __restrict__ p
       const float b = (float)__builtin_bit_cast(_Float16, (uint16_t)(w0 >> 16));
       const float c = (float)__builtin_bit_cast(_Float16, (uint16_t)(w1 & 0xffff));
       const float d = (float)__builtin_bit_cast(_Float16, (uint16_t)(w1 >> 16));
-      p0[2 * j] -= step * a + wd_step * p0[2 * j];
-      p0[2 * j + 1] -= step * b + wd_step * p0[2 * j + 1];
-      p1[2 * j] -= step * c + wd_step * p1[2 * j];
-      p1[2 * j + 1] -= step * d + wd_step * p1[2 * j + 1];
+      p0[2 * j] = sgd_tail<false>(a, p0[2 * j], nullptr, lr, gscale, 0.f, wd, 0);
+      p0[2 * j + 1] = sgd_tail<false>(b, p0[2 * j + 1], nullptr, lr, gscale, 0.f, wd, 0);
+      p1[2 * j] = sgd_tail<false>(c, p1[2 * j], nullptr, lr, gscale, 0.f, wd, 0);
+      p1[2 * j + 1] = sgd_tail<false>(d, p1[2 * j + 1], nullptr, lr, gscale, 0.f, wd, 0);
     }
     reinterpret_cast<f32x4*>(p)[2 * i] = p0;
     reinterpret_cast<f32x4*>(p)[2 * i + 1] = p1;
@@ -100,7 +111,7 @@ __global__ __launch_bounds__(256) void sgd_apply_multi_kernel(float* __restrict_
 
 // vectorised fp16-wire form (no momentum / weight decay): 8 elements per lane, every source's
 // 16-byte chunk loaded before the fixed-order sum
-// (same arithmetic as sgd_apply_multi_kernel: d = sum * gscale, p -= lr * d)
+// (same arithmetic as sgd_apply_multi_kernel: sgd_tail on the fp32 sum)
 template <bool IMG>
 __global__ __launch_bounds__(256) void sgd_apply_multi_h8_kernel(float* __restrict__ p, SrcList srcs, size_t n,
                                                                  float lr, float gscale, uint16_t* __restrict__ img) {
@@ -109,7 +120,7 @@ __global__ __launch_bounds__(256) void sgd_apply_multi_h8_kernel(float* __restri
     const size_t i = (n8 << 3) + threadIdx.x;
     float s = 0.f;
     for (int k = 0; k < srcs.n; ++k) s += ld_grad(reinterpret_cast<const uint16_t*>(srcs.p[k]), i);
-    const float nv = p[i] - lr * (s * gscale);
+    const float nv = sgd_tail<false>(s, p[i], nullptr, lr, gscale, 0.f, 0.f, 0);
     p[i] = nv;
     if (IMG) img[i] = f2bf(nv);
   }
@@ -127,8 +138,8 @@ __global__ __launch_bounds__(256) void sgd_apply_multi_h8_kernel(float* __restri
     f32x4 p1 = reinterpret_cast<f32x4*>(p)[2 * i + 1];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      p0[j] -= lr * (s[j] * gscale);
-      p1[j] -= lr * (s[4 + j] * gscale);
+      p0[j] = sgd_tail<false>(s[j], p0[j], nullptr, lr, gscale, 0.f, 0.f, 0);
+      p1[j] = sgd_tail<false>(s[4 + j], p1[j], nullptr, lr, gscale, 0.f, 0.f, 0);
     }
     reinterpret_cast<f32x4*>(p)[2 * i] = p0;
     reinterpret_cast<f32x4*>(p)[2 * i + 1] = p1;
@@ -150,7 +161,7 @@ __global__ __launch_bounds__(256) void aggregate_kernel(const ST* const* __restr
     s *= scale;
     if constexpr (sizeof(DT) == 2) {
       if (accumulate) s += ld_grad(dst, i);
-      dst[i] = __builtin_bit_cast(uint16_t, (_Float16)s);
+      dst[i] = f2h(s);
     } else {
       if (accumulate) s += dst[i];
       dst[i] = s;
@@ -161,7 +172,7 @@ __global__ __launch_bounds__(256) void aggregate_kernel(const ST* const* __restr
 __global__ __launch_bounds__(256) void fp16_pack_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst,
                                                         size_t n, float scale) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    dst[i] = __builtin_bit_cast(uint16_t, (_Float16)(src[i] * scale));
+    dst[i] = f2h(src[i] * scale);
 }
 __global__ __launch_bounds__(256) void fp16_unpack_kernel(const uint16_t* __restrict__ src, float* __restrict__ dst,
                                                           size_t n, float scale) {
@@ -367,10 +378,10 @@ int psx_sgd_apply(float* p, const void* g, float* buf, long n, float lr, float g
       ((uintptr_t)img % 16 == 0)) {
     if (im)
       hipLaunchKernelGGL(sgd_apply_h8_kernel<true>, dim3(grid_for(n / 8)), dim3(256), 0, st, p, (const uint16_t*)g,
-                         (size_t)n, lr * gscale, lr * wd, im);
+                         (size_t)n, lr, gscale, wd, im);
     else
       hipLaunchKernelGGL(sgd_apply_h8_kernel<false>, dim3(grid_for(n / 8)), dim3(256), 0, st, p, (const uint16_t*)g,
-                         (size_t)n, lr * gscale, lr * wd, im);
+                         (size_t)n, lr, gscale, wd, im);
     return (int)hipGetLastError();
   }
   const int grid = grid_for(n);

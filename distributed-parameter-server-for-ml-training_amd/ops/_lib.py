@@ -85,6 +85,7 @@ _KERNEL_SIGS = {
     "psx_sgd_apply_multi": (i32, [vp, vp, i32, vp, i64, f32, f32, f32, f32, i32, i32, vp, vp]),
     "psx_fp16_pack": (i32, [vp, vp, i64, f32, vp]),
     "psx_fp16_unpack": (i32, [vp, vp, i64, f32, vp]),
+    "psx_gather_f32": (i32, [vp, vp, i64, vp, vp]),
     "psx_param_unpack": (i32, [vp, vp, i32, vp, vp]),
     "psx_param_unpack_tiles": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, i64, vp, i32, vp, i32, vp]),
     "psx_unpack_desc_size": (i32, []),

@@ -957,6 +957,14 @@ def fp16_unpack(src, dst, scale=1.0):
     check(kernels().psx_fp16_unpack(ptr(src), ptr(dst), src.numel(), float(scale), stream_ptr()), "fp16_unpack")
 
 
+def gather_f32(src, idx, dst):
+    """dst[i] = src[idx[i]] (fp32, int64 indices): the kernel the native server loops use for the
+    fp32 remainder of a fetch (csrc/server/event_loop.cpp, sync_loop.cpp)."""
+    assert src.dtype == torch.float32 and dst.dtype == torch.float32 and idx.dtype == torch.int64, "gather_f32"
+    assert dst.numel() >= idx.numel() and src.device == idx.device == dst.device, "gather_f32"
+    check(kernels().psx_gather_f32(ptr(src), ptr(idx), idx.numel(), ptr(dst), stream_ptr()), "gather_f32")
+
+
 def param_unpack(arena, descs_dev, ndesc, wbuf):
     check(kernels().psx_param_unpack(ptr(arena), ptr(descs_dev), ndesc, ptr(wbuf), stream_ptr()), "param_unpack")
 
