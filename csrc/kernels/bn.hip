@@ -261,9 +261,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
   }
 }
 
-// Opt-in (PSX_TUNE bnfin_apply=1) variant of bn_apply_kernel with the training-mode finalize folded in:
-// every workgroup computes the affine(s) from the stat slots (bnfin.hpp bn_fin_lds). Separate
-// kernels so the default path keeps its exact code (an A/B showed +38 us/step otherwise).
+// The engine's default training-mode apply (engine.py fin_apply): bn_apply_kernel with the finalize
+// folded in: every workgroup computes the affine(s) from the stat slots (bnfin.hpp bn_fin_lds).
+// Separate kernels so the plain apply (eval mode, the separate-finalize path) keeps its exact
+// code (an A/B showed +38 us/step otherwise).
 template <typename T, int MODE, bool RELU, bool FIN = true>
 __global__ __launch_bounds__(256) void bn_apply_fin_kernel(const T* __restrict__ y, const float* __restrict__ scale,
                                                        const float* __restrict__ shift, const T* __restrict__ res,
@@ -325,8 +326,8 @@ __global__ __launch_bounds__(256) void bn_apply_fin_kernel(const T* __restrict__
   }
 }
 
-// Opt-in variant of bn_bwd_apply_kernel: coefficients from the slot sums part [T][NS][C] per
-// workgroup (bnfin.hpp bn_bwd_fin_lds).
+// The engine's default backward apply (engine.py fin_apply): bn_bwd_apply_kernel with the
+// coefficients from the slot sums part [T][NS][C] per workgroup (bnfin.hpp bn_bwd_fin_lds).
 template <typename T, bool MASK, bool TWO, bool DZOUT, bool FIN = true>
 __global__ __launch_bounds__(256) void bn_bwd_apply_fin_kernel(const T* __restrict__ g, const T* __restrict__ o,
                                                            const T* __restrict__ y1,

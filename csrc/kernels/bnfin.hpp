@@ -237,7 +237,8 @@ PSX_DEV void bn_bwd_finalize_block(const float* part, int NS, int which, const B
 }
 
 // ---------------------------------------------------------------------------------------
-// Consumer-side finalize: every workgroup of the BN-apply launch that consumes a layer's slot
+// Consumer-side finalize (the engine's default, engine.py fin_apply; the producer-side form
+// above is a test switch, fuse_fin): every workgroup of the BN-apply launch that consumes a layer's slot
 // sums recomputes the per-channel affine (forward) or coefficients (backward) into LDS, and
 // workgroup 0 also writes the global side outputs (affine, saved statistics, running
 // statistics / coefficients, dgamma and dbeta on the gradient wire). This replaces one
