@@ -26,9 +26,11 @@ import torch
 
 from ..utils import checkpoint as ckpt
 from ..utils import metrics as M
+from ..ops import kernels as K
 from ..utils import trace
 from . import control as CP
 from . import q8, topk
+from . import rules as R
 from .core import APPLY, WAIT, ServerCore
 
 _TRACE = os.environ.get("PSX_TRACE", "0") == "1"
@@ -63,54 +65,30 @@ class ParameterServer:
         self.params = self.arena[: self.n]
         self.momentum_buf = torch.zeros_like(self.params) if cfg.momentum else None
         self._mom_first = True
-        self.agg = None  # fp32 aggregation buffer for in-process sync rounds
-        # --optimizer lars: every whole-arena update goes through _lars_update (the LARS pair of
-        # csrc/kernels/lars.hip, staged through agg); its only state is the momentum buffer
-        self._lars = cfg.optimizer == "lars"
-        self._lars_tab = None      # device segment table + scratch (ops/kernels.py LarsTable)
-        self._lars_ratios = None   # CPU arena: the last update's trust ratios of the adapted tensors
-        self._lars_applied = False
-        if self._lars:
-            self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device)
-            if self.device.type == "cuda":
-                from ..ops import kernels as K
-
-                self._lars_tab = K.lars_table(layout, self.device)
-        # --optimizer adamw: element-wise, so every range of every path goes through _adamw_range
-        # (csrc/kernels/adamw.hip); state: both moments and the count of completed updates
-        self._adamw = cfg.optimizer == "adamw"
-        self.adam_m = self.adam_v = None
+        # the one update rule of this server (parallel/rules.py): update_range runs it on every route
+        self.rule = R.rule_of(cfg)
+        # fp32 aggregation buffer: whole-arena rules stage every round's sum through it; otherwise
+        # allocated when a path first needs it (in-process sync rounds, decoded payloads)
+        self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device) if self.rule.whole else None
+        # --optimizer lars / lamb: per-tensor ratios, in the device segment table + scratch
+        # (ops/kernels.py LarsTable) or, on a CPU arena, the last update's list of the adapted tensors
+        self._lars_tab = K.lars_table(layout, self.device) if self.rule.table and self.device.type == "cuda" else None
+        self._lars_ratios = self._lamb_ratios = None
+        self._ratios_applied = False
+        # --optimizer adamw / lamb: both moments and the count of completed updates
+        self.adam_m = torch.zeros_like(self.params) if self.rule.adam else None
+        self.adam_v = torch.zeros_like(self.params) if self.rule.adam else None
         self.adam_t = 0
-        # --optimizer lamb: the AdamW moments under the LARS table; every whole-arena update goes
-        # through _lamb_update (the pair of csrc/kernels/lamb.hip, staged through agg)
-        self._lamb = cfg.optimizer == "lamb"
-        self._lamb_ratios = None   # CPU arena: the last update's ratios of the adapted tensors
-        self._lamb_applied = False
-        if self._lamb:
-            self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device)
-            if self.device.type == "cuda":
-                from ..ops import kernels as K
-
-                self._lars_tab = K.lars_table(layout, self.device)
-        if self._adamw or self._lamb:
-            self.adam_m = torch.zeros_like(self.params)
-            self.adam_v = torch.zeros_like(self.params)
-        # --clip-norm / --skip-nonfinite: every whole-arena update goes through _guard_update (the
-        # three launches of csrc/kernels/gguard.hip, staged through agg); no parameter state, only
-        # the counters: in the device state block, or in _guard_host on a CPU arena
+        # --clip-norm / --skip-nonfinite: no parameter state, only the counters: in the device state
+        # block (ops/kernels.py GuardState), or in _guard_host on a CPU arena
         self._guard = cfg.grad_guard
-        self._guard_state = None   # device scratch + state block (ops/kernels.py GuardState)
-        self._guard_host = None
+        self._guard_state = self._guard_host = None
         self._guard_skip_logged = False
-        if self._guard:
-            self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device)
-            if self.device.type == "cuda":
-                from ..ops import kernels as K
-
-                self._guard_state = K.GuardState(self.n, self.device)
-            else:
-                self._guard_host = {"rounds": 0, "clipped_rounds": 0, "skipped_rounds": 0, "norm_last": 0.0,
-                                    "norm_max": 0.0, "norm_sum": 0.0}
+        if self._guard and self.device.type == "cuda":
+            self._guard_state = K.GuardState(self.n, self.device)
+        elif self._guard:
+            self._guard_host = {"rounds": 0, "clipped_rounds": 0, "skipped_rounds": 0, "norm_last": 0.0,
+                                "norm_max": 0.0, "norm_sum": 0.0}
         # --dc-lambda (async): delay compensation (csrc/kernels/dcasgd.hip). Every fetch leaves the
         # worker's backup of the fp32 parameters (note_fetch); the apply of a push from a worker
         # with a valid backup is g + lam * g * g * (w - bak) in place of g (_apply_dc).
@@ -161,8 +139,7 @@ class ParameterServer:
             self._apply_dc(grads, weight, worker_id)
             return self.finish_round_apply(self._time_end(t0))
         if grads.dtype == torch.int32:  # top-k payload (parallel/topk.py)
-            if not self.cfg.momentum and not self.cfg.weight_decay and not self._lars and not self._guard \
-                    and not self._adamw and not self._lamb:
+            if self.rule.scatters(self.cfg):
                 # no optimizer state: scatter straight into the fp32 master parameters
                 topk.decode_add(grads, self.params, -self.lr * weight, self._kcap)
                 self._wire_stale = True  # the bf16 image was not written by this update
@@ -175,22 +152,45 @@ class ParameterServer:
         return self.finish_round_apply(self._time_end(t0))
 
     def _apply_q8(self, payloads: list, weight: float):
-        """The update from q8 payloads, decoded and summed in fp32 in list order: one fused
-        launch on the device (the weight image, when enabled, written in the same pass); the
-        torch decode into the aggregation buffer on a CPU arena. LARS: decoded into the
-        aggregation buffer on either, then the dense entry of the LARS pair; the gradient guard
-        likewise (its dense entry), AdamW (the one-source fp32 form of its kernel) and LAMB (its
-        dense entry)."""
-        if self.device.type == "cuda" and not self._lars and not self._guard and not self._adamw and not self._lamb:
-            from ..ops import kernels as K
+        """The update from q8 payloads, decoded and summed in fp32 in list order (update_range)."""
+        self.update_range(payloads, weight, 0, self.n)
 
-            img = self.wire.img[: self.n] if self.wire is not None else None
-            K.q8_apply_multi(self.params, payloads, self.lr, gscale=weight, momentum=self.cfg.momentum,
-                             wd=self.cfg.weight_decay, buf=self.momentum_buf, first=self._mom_first, n=self.n, img=img)
+    # ------------------------------------------------------------------ the one update entry
+    _IMG_OF_WIRE = object()
+
+    def update_range(self, srcs: list, weight: float, lo: int, hi: int, img=_IMG_OF_WIRE, summed: bool = False):
+        """The update of params[lo:hi] by this server's rule (parallel/rules.py); every route ends
+        here. ``srcs``: fp16 / fp32 wires that each hold the gradient of exactly that range in their
+        first hi - lo elements, summed in fp32 in list order, or the aggregation buffer itself (a
+        decoded or accumulated sum); ``summed``: the one source already is the round's sum, taken
+        as is. q8 payloads (whole range): decoded inside the kernel by a rule that has such a
+        device form, otherwise into the aggregation buffer first. A rule that needs the whole arena
+        refuses a partial range. ``img``: the bf16 image slice that receives the updated range, on
+        the device in the same pass (default: the weight wire's, which an ``img`` of the caller's,
+        and every host form, leaves stale). Several ranges of one round share the momentum 'first
+        step' flag and the Adam update number: finish_round_apply closes the round."""
+        rule = self.rule
+        if rule.whole and (lo, hi) != (0, self.n):
+            raise ValueError(rule.refusal.format(lo=lo, hi=hi, n=self.n))
+        if hi <= lo:
             return
-        for i, p in enumerate(payloads):
-            self._dense_of(p, add=i > 0)
-        self.apply_range(self.agg, weight, 0, self.n)
+        on_device, own_img = self.device.type == "cuda", img is not self._IMG_OF_WIRE
+        if on_device and not own_img:
+            img = self.wire.img[lo:hi] if self.wire is not None else None
+        if srcs[0].dtype == torch.uint8:
+            if on_device and rule.device_q8 is not None:
+                return rule.device_q8(self, srcs, weight, img)
+            for i, p in enumerate(srcs):
+                self._dense_of(p, add=i > 0)
+            srcs, summed = [self.agg], True
+        if on_device:
+            rule.device(self, srcs, weight, lo, hi, img, summed)
+        elif rule.host(self, srcs, weight, lo, hi, summed) is False:
+            return  # a skipped round: parameters and images are as they were
+        elif own_img and img is not None:
+            img.copy_(self.params[lo:hi])  # RNE, same bits as the kernels' f2bf
+        if self.wire is not None and (own_img or not on_device):
+            self._wire_stale = True  # the wire's image was not written by this update
 
     # ------------------------------------------------------------------ delay compensation (--dc-lambda)
     def note_fetch(self, worker_id: int, dst: torch.Tensor | None = None) -> int:
@@ -210,8 +210,6 @@ class ParameterServer:
             dst.dtype == torch.float32 and dst.device == self.arena.device and dst.is_contiguous()
             and dst.numel() == self.arena.numel())))
         if fused:
-            from ..ops import kernels as K
-
             K.dc_fetch_copy(self.arena, dst, bak, self.n)
         else:
             bak.copy_(self.params)
@@ -239,8 +237,6 @@ class ParameterServer:
         if bak is None and self._dc_ms is None:  # nothing of the DC form is left: the plain update
             return self.apply_range(g, weight, 0, self.n)
         if self.device.type == "cuda":
-            from ..ops import kernels as K
-
             img = self.wire.img[: self.n] if self.wire is not None else None
             K.dc_apply(self.params, g, bak, self.lr, cfg.dc_lambda, ms=self._dc_ms, decay=cfg.dc_decay,
                        eps=cfg.dc_eps, gscale=weight, momentum=cfg.momentum, wd=cfg.weight_decay,
@@ -305,9 +301,7 @@ class ParameterServer:
     def _dense_of(self, payload: torch.Tensor, out: torch.Tensor | None = None, add: bool = False):
         """Top-k / q8 payload -> dense fp32 gradient (into the aggregation buffer by default)."""
         if out is None:
-            if self.agg is None:
-                self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device)
-            out = self.agg
+            out = self._agg()
         if payload.dtype == torch.uint8:
             return q8.decode(payload, self.n, out=out, add=add)
         if not add:
@@ -318,315 +312,20 @@ class ParameterServer:
         """The update restricted to params[lo:hi] (g holds exactly that slice): one bucket of a
         backward-overlapped sync round (parallel/overlap.py). Several ranges of one round share
         the same momentum 'first step' flag; finish_round_apply closes the round."""
-        if self._lars:
-            self._lars_whole(lo, hi)
-            return self._lars_update([g], weight)
-        if self._lamb:
-            self._lamb_whole(lo, hi)
-            return self._lamb_update([g], weight)
-        if self._guard:
-            self._guard_whole(lo, hi)
-            return self._guard_update([g], weight)
-        self._sgd_range(g, weight, lo, hi)
-
-    def _sgd_range(self, g: torch.Tensor, weight: float, lo: int, hi: int):
-        """apply_range's plain SGD form (no LARS, no guard routing); AdamW's under --optimizer adamw."""
-        if self._adamw:
-            return self._adamw_range([g], weight, lo, hi)
-        p = self.params[lo:hi]
-        buf = self.momentum_buf[lo:hi] if self.momentum_buf is not None else None
-        if self.device.type == "cuda":
-            from ..ops import kernels as K
-
-            img = self.wire.img[lo:hi] if self.wire is not None else None  # fetch image, same pass
-            K.sgd_apply(p, g, self.lr, gscale=weight, momentum=self.cfg.momentum, wd=self.cfg.weight_decay, buf=buf,
-                        first=self._mom_first, n=hi - lo, img=img)
-            return
-        if self.wire is not None:
-            self._wire_stale = True
-        d = g.to(torch.float32) * weight
-        if self.cfg.weight_decay:
-            d = d + self.cfg.weight_decay * p
-        if buf is not None:
-            if self._mom_first:
-                buf.copy_(d)
-            else:
-                buf.mul_(self.cfg.momentum).add_(d)
-            d = buf
-        p.sub_(self.lr * d)
+        self.update_range([g], weight, lo, hi, summed=True)
 
     def apply_range_sources(self, srcs: list, weight: float, lo: int, hi: int):
         """apply_range of the fp32 sum of several wires' [lo:hi] (fixed list order): one bucket
         of an overlapped round whose wires were gathered (parallel/overlap.py)."""
-        if self._lars:
-            self._lars_whole(lo, hi)
-            return self._lars_update(list(srcs), weight)
-        if self._lamb:
-            self._lamb_whole(lo, hi)
-            return self._lamb_update(list(srcs), weight)
-        if self._guard:
-            self._guard_whole(lo, hi)
-            return self._guard_update(list(srcs), weight)
-        if self._adamw:
-            return self._adamw_range([s[lo:hi] for s in srcs], weight, lo, hi)
-        if self.device.type == "cuda":
-            from ..ops import kernels as K
-
-            buf = self.momentum_buf[lo:hi] if self.momentum_buf is not None else None
-            img = self.wire.img[lo:hi] if self.wire is not None else None
-            K.sgd_apply_multi(self.params[lo:hi], [s[lo:hi] for s in srcs], self.lr, gscale=weight,
-                              momentum=self.cfg.momentum, wd=self.cfg.weight_decay, buf=buf, first=self._mom_first,
-                              n=hi - lo, img=img)
-            return
-        agg = torch.zeros(hi - lo, dtype=torch.float32, device=self.device)
-        for s in srcs:  # fixed order, fp32 accumulation
-            agg.add_(s[lo:hi].to(torch.float32))
-        self.apply_range(agg, weight, lo, hi)
-
-    # ------------------------------------------------------------------ AdamW (--optimizer adamw)
-    _IMG_OF_WIRE = object()
-
-    def _adamw_range(self, srcs: list, weight: float, lo: int, hi: int, img=_IMG_OF_WIRE):
-        """The AdamW update of params[lo:hi] from sources that each hold exactly that slice (fp16 /
-        fp32 wires summed in fp32 in list order, or one dense fp32 sum), update number adam_t + 1:
-        g = weight * s; m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g g;
-        p = p (1 - lr wd) - lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps).
-        Element-wise: any range is legal, and every range of one round shares t
-        (finish_round_apply closes the round). ``img``: the bf16 image slice to write (default: the
-        weight wire's). Device: one launch of csrc/kernels/adamw.hip; CPU arena: the same formula in
-        torch fp32 from the same eight fp32 scalars (equal to a tolerance, not bit for bit)."""
-        import numpy as np
-
-        from ..ops import kernels as K
-
-        cfg = self.cfg
-        n, t = hi - lo, self.adam_t + 1
-        if n <= 0:
-            return
-        p, m, v = self.params[lo:hi], self.adam_m[lo:hi], self.adam_v[lo:hi]
-        hp = dict(beta1=cfg.adam_beta1, beta2=cfg.adam_beta2, eps=cfg.adam_eps, wd=cfg.weight_decay)
-        if self.device.type == "cuda":
-            if img is self._IMG_OF_WIRE:
-                img = self.wire.img[lo:hi] if self.wire is not None else None
-            K.adamw_apply_multi(p, [s[:n] for s in srcs], m, v, self.lr, t, gscale=weight, n=n, img=img, **hp)
-            return
-        try:
-            step_size, b1, omb1, b2, omb2, rbc2, eps, decay = K.adamw_scalars(self.lr, t, **hp)
-        except (OSError, RuntimeError, AttributeError):  # the kernel library is not loaded here
-            step_size, b1, omb1, b2, omb2, rbc2, eps, decay = K.adamw_scalars_host(self.lr, t, **hp)
-        if self.wire is not None:
-            self._wire_stale = True
-        s = torch.zeros(n, dtype=torch.float32, device=self.device)
-        for x in srcs:  # fixed order, fp32 accumulation
-            s = s + x[:n].to(torch.float32)
-        # plain element-wise fp32 ops only (no fused alpha forms): a range gives the whole round's bits
-        g = s * float(np.float32(weight))
-        m.copy_(m * b1 + g * omb1)
-        v.copy_(v * b2 + (g * g) * omb2)
-        den = v.sqrt() * rbc2 + eps
-        p.copy_(p * decay - (m / den) * step_size)
-
-    # ------------------------------------------------------------------ LARS (--optimizer lars)
-    def _lars_whole(self, lo: int, hi: int):
-        if (lo, hi) != (0, self.n):
-            raise ValueError(f"--optimizer lars needs every tensor's norm before its first element moves: a partial "
-                             f"range [{lo}, {hi}) of {self.n} cannot be applied (no bucketed or sharded updates)")
-
-    def _lars_update(self, srcs: list, weight: float):
-        """The whole-arena LARS update from dense wires (fp16 / fp32, summed in fp32 in list
-        order) or from the aggregation buffer itself (a decoded or accumulated sum):
-        d = lambda_t * (weight * s + wd * w) for tensors with ndim > 1, lambda_t = trust * |w| /
-        (weight * |s| + wd * |w| + eps) (1 when a norm is 0); d = weight * s for 1-D tensors;
-        then the momentum form of apply_range. Device: the two launches of csrc/kernels/lars.hip;
-        CPU arena: the same formula in torch, tensor by tensor (equal to a tolerance, not bit for
-        bit: the reduction orders differ)."""
-        cfg = self.cfg
-        self._lars_applied = True
-        staged = len(srcs) == 1 and srcs[0].dtype == torch.float32 and srcs[0].data_ptr() == self.agg.data_ptr()
-        if self.device.type == "cuda":
-            from ..ops import kernels as K
-
-            kw = dict(lr=self.lr, gscale=weight, momentum=cfg.momentum, wd=cfg.weight_decay, trust=cfg.lars_trust,
-                      eps=cfg.lars_eps, buf=self.momentum_buf, first=self._mom_first, n=self.n,
-                      img=self.wire.img[: self.n] if self.wire is not None else None)
-            if staged:
-                K.lars_apply(self.params, self.agg, self._lars_tab, **kw)
-            else:
-                K.lars_apply_multi(self.params, [s[: self.n] for s in srcs], self.agg, self._lars_tab, **kw)
-            return
-        if not staged:
-            self.agg.zero_()
-            for s in srcs:  # fixed order, fp32 accumulation
-                self.agg.add_(s[: self.n].to(torch.float32))
-        if self.wire is not None:
-            self._wire_stale = True
-        ratios = []
-        for e in self.layout.entries.values():
-            if e.region != "param" or not e.numel:
-                continue
-            w = self.params[e.offset:e.offset + e.numel]
-            d = self.agg[e.offset:e.offset + e.numel] * weight
-            if len(e.shape) > 1:
-                wn, gn = float(w.double().norm()), float(d.double().norm())
-                lam = cfg.lars_trust * wn / (gn + cfg.weight_decay * wn + cfg.lars_eps) if wn > 0 and gn > 0 else 1.0
-                ratios.append(lam)
-                if cfg.weight_decay:
-                    d = d + cfg.weight_decay * w
-                d = d * lam
-            if self.momentum_buf is not None:
-                buf = self.momentum_buf[e.offset:e.offset + e.numel]
-                if self._mom_first:
-                    buf.copy_(d)
-                else:
-                    buf.mul_(cfg.momentum).add_(d)
-                d = buf
-            w.sub_(self.lr * d)
-        self._lars_ratios = ratios
+        self.update_range([s[lo:hi] for s in srcs], weight, lo, hi)
 
     def lars_trust_ratios(self):
-        """{min, median, max} of the last update's trust ratios over the adapted tensors (read
-        from the device ratio table here, not per round); None before the first update."""
-        if not self._lars_applied:
-            return None
-        if self._lars_tab is not None:
-            r = self._lars_tab.ratios.cpu()[torch.tensor(self._lars_tab.adapt)]
-        else:
-            r = torch.tensor(self._lars_ratios)
-        if not r.numel():
-            return None
-        return {"min": float(r.min()), "median": float(r.median()), "max": float(r.max())}
-
-    # ------------------------------------------------------------------ LAMB (--optimizer lamb)
-    def _lamb_whole(self, lo: int, hi: int):
-        if (lo, hi) != (0, self.n):
-            raise ValueError(f"--optimizer lamb needs every tensor's norm before its first element moves: a partial "
-                             f"range [{lo}, {hi}) of {self.n} cannot be applied (no bucketed or sharded updates)")
-
-    def _lamb_update(self, srcs: list, weight: float):
-        """The whole-arena LAMB update (You et al. 2020), number adam_t + 1, from dense wires (fp16
-        / fp32, summed in fp32 in list order) or from the aggregation buffer itself (a decoded or
-        accumulated sum): g = weight * s; m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g g;
-        r = m / (1 - beta1^t) / (sqrt(v) / sqrt(1 - beta2^t) + eps); tensors with ndim > 1: u = r +
-        wd * w, phi = |w| / |u| (1 when a norm is 0); 1-D tensors: u = r, phi = 1; w -= lr * phi * u.
-        No clamp on |w|, no global gradient normalisation. Device: the two launches of
-        csrc/kernels/lamb.hip (the aggregation buffer ends holding u); CPU arena: the same formula
-        in torch from the same fp32 scalars, tensor by tensor (equal to a tolerance, not bit for
-        bit: the reduction orders differ)."""
-        import numpy as np
-
-        from ..ops import kernels as K
-
-        cfg = self.cfg
-        self._lamb_applied = True
-        t = self.adam_t + 1
-        hp = dict(beta1=cfg.adam_beta1, beta2=cfg.adam_beta2, eps=cfg.adam_eps)
-        staged = len(srcs) == 1 and srcs[0].dtype == torch.float32 and srcs[0].data_ptr() == self.agg.data_ptr()
-        if self.device.type == "cuda":
-            kw = dict(lr=self.lr, t=t, gscale=weight, wd=cfg.weight_decay, n=self.n,
-                      img=self.wire.img[: self.n] if self.wire is not None else None, **hp)
-            if staged:
-                K.lamb_apply(self.params, self.agg, self.adam_m, self.adam_v, self._lars_tab, **kw)
-            else:
-                K.lamb_apply_multi(self.params, [s[: self.n] for s in srcs], self.agg, self.adam_m, self.adam_v,
-                                   self._lars_tab, **kw)
-            return
-        if not staged:
-            self.agg.zero_()
-            for s in srcs:  # fixed order, fp32 accumulation
-                self.agg.add_(s[: self.n].to(torch.float32))
-        if self.wire is not None:
-            self._wire_stale = True
-        try:
-            bc1, b1, omb1, b2, omb2, rbc2, eps, _ = K.lamb_scalars(t, **hp)
-        except (OSError, RuntimeError, AttributeError):  # the kernel library is not loaded here
-            bc1, b1, omb1, b2, omb2, rbc2, eps, _ = K.lamb_scalars_host(t, **hp)
-        lr, wd = float(np.float32(self.lr)), float(np.float32(cfg.weight_decay))
-        g = self.agg * float(np.float32(weight))
-        self.adam_m.copy_(self.adam_m * b1 + g * omb1)
-        self.adam_v.copy_(self.adam_v * b2 + (g * g) * omb2)
-        r = (self.adam_m / (self.adam_v.sqrt() * rbc2 + eps)) * bc1
-        ratios = []
-        for e in self.layout.entries.values():
-            if e.region != "param" or not e.numel:
-                continue
-            w = self.params[e.offset:e.offset + e.numel]
-            u = r[e.offset:e.offset + e.numel]
-            phi = 1.0
-            if len(e.shape) > 1:
-                u = u + wd * w
-                wn, un = float(w.double().norm()), float(u.double().norm())
-                phi = float(np.float32(wn / un)) if wn > 0 and un > 0 else 1.0
-                ratios.append(phi)
-            w.sub_(float(np.float32(lr * phi)) * u)
-        self._lamb_ratios = ratios
+        """{min, median, max} of the last LARS update's trust ratios (rules.trust_ratios)."""
+        return R.trust_ratios(self, R.LARS, self._lars_ratios)
 
     def lamb_trust_ratios(self):
-        """{min, median, max} of the last update's ratios |w| / |u| over the adapted tensors (read
-        from the device ratio table here, not per round); None before the first update."""
-        if not self._lamb_applied:
-            return None
-        if self._lars_tab is not None:
-            r = self._lars_tab.ratios.cpu()[torch.tensor(self._lars_tab.adapt)]
-        else:
-            r = torch.tensor(self._lamb_ratios)
-        if not r.numel():
-            return None
-        return {"min": float(r.min()), "median": float(r.median()), "max": float(r.max())}
-
-    # ------------------------------------------------------------------ gradient guard (--clip-norm, --skip-nonfinite)
-    def _guard_whole(self, lo: int, hi: int):
-        if (lo, hi) != (0, self.n):
-            raise ValueError(f"--clip-norm / --skip-nonfinite need the whole gradient's norm before the first parameter "
-                             f"moves: a partial range [{lo}, {hi}) of {self.n} cannot be applied (no bucketed or "
-                             f"sharded updates)")
-
-    def _guard_update(self, srcs: list, weight: float):
-        """The whole-arena guarded update from dense wires (fp16 / fp32, summed in fp32 in list
-        order) or from the aggregation buffer itself (a decoded or accumulated sum):
-        S = sum s^2, norm = weight * sqrt(S); S not finite: the round is skipped (parameters,
-        momentum buffer and fetch image untouched; it still counts as a round, and consumes the
-        momentum 'first step' flag: the buffer starts as zeros, so momentum * 0 + d of the next
-        round has the value the first-step form would have given); else coef = min(1, clip_norm /
-        (norm + 1e-6)) (1 without --clip-norm), rounded to fp32, and apply_range's update with
-        weight * coef (one fp32 multiply): weight decay is added after the scaling, not clipped.
-        Device: the three launches of csrc/kernels/gguard.hip, no host synchronisation; CPU arena:
-        the same formula in torch (equal to a tolerance, not bit for bit: the reduction orders
-        differ)."""
-        cfg = self.cfg
-        staged = len(srcs) == 1 and srcs[0].dtype == torch.float32 and srcs[0].data_ptr() == self.agg.data_ptr()
-        if self.device.type == "cuda":
-            from ..ops import kernels as K
-
-            kw = dict(lr=self.lr, gscale=weight, momentum=cfg.momentum, wd=cfg.weight_decay, clip_norm=cfg.clip_norm,
-                      buf=self.momentum_buf, first=self._mom_first, n=self.n,
-                      img=self.wire.img[: self.n] if self.wire is not None else None)
-            if staged:
-                K.guard_apply(self.params, self.agg, self._guard_state, **kw)
-            else:
-                K.guard_apply_multi(self.params, [s[: self.n] for s in srcs], self.agg, self._guard_state, **kw)
-            return
-        import math
-
-        import numpy as np
-
-        if not staged:
-            self.agg.zero_()
-            for s in srcs:  # fixed order, fp32 accumulation
-                self.agg.add_(s[: self.n].to(torch.float32))
-        S = float(self.agg.double().square().sum())
-        h = self._guard_host
-        h["rounds"] += 1
-        if not math.isfinite(S):
-            h["skipped_rounds"] += 1
-            h["norm_last"] = float("nan") if S != S else float("inf")
-            return
-        norm = float(np.float32(weight)) * math.sqrt(S)
-        coef = np.float32(min(1.0, cfg.clip_norm / (norm + 1e-6))) if cfg.clip_norm > 0 else np.float32(1.0)
-        h["clipped_rounds"] += int(coef < 1.0)
-        h["norm_last"] = norm
-        h["norm_max"] = max(h["norm_max"], norm)
-        h["norm_sum"] += norm
-        self._sgd_range(self.agg, float(np.float32(weight) * coef), 0, self.n)
+        """{min, median, max} of the last LAMB update's ratios |w| / |u| (rules.trust_ratios)."""
+        return R.trust_ratios(self, R.LAMB, self._lamb_ratios)
 
     def guard_counters(self):
         """The guard's running counters (read from the device state block here, not per round);
@@ -649,7 +348,7 @@ class ParameterServer:
         """Closes one update (global_step + 1). ``dt`` >= 0: its host-measured time (CPU arena);
         else the device ranges timed since the last close (deferred), or none (graph capture)."""
         self._mom_first = False
-        if self._adamw or self._lamb:
+        if self.rule.adam:
             self.adam_t += 1
         if self._round_ev:
             self._ev_pending = self._ev_pending + [self._round_ev]
@@ -660,16 +359,18 @@ class ParameterServer:
         self.core.on_applied(dt)
         return dt
 
-    def _accumulate(self, grads: torch.Tensor, first: bool):
+    def _agg(self) -> torch.Tensor:
         if self.agg is None:
             self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+        return self.agg
+
+    def _accumulate(self, grads: torch.Tensor, first: bool):
         if grads.dtype in (torch.int32, torch.uint8):
-            self._dense_of(grads, self.agg, add=not first)
-            return
-        if first:
-            self.agg.copy_(grads[: self.n])
+            self._dense_of(grads, add=not first)
+        elif first:
+            self._agg().copy_(grads[: self.n])
         else:
-            self.agg.add_(grads[: self.n].to(torch.float32))
+            self._agg().add_(grads[: self.n].to(torch.float32))
 
     # ------------------------------------------------------------------ RPC surface
     def register_worker(self, worker_name: str = "worker-node", requested_id: int = -1):
@@ -840,28 +541,7 @@ class ParameterServer:
             return False
         trace.mark("psx.apply")
         t0 = self._time_begin()
-        if self._lars:
-            self._lars_update(list(srcs), res.weight)
-        elif self._lamb:
-            self._lamb_update(list(srcs), res.weight)
-        elif self._guard:
-            self._guard_update(list(srcs), res.weight)
-        elif self._adamw:
-            self._adamw_range([s[: self.n] for s in srcs], res.weight, 0, self.n)
-        elif self.device.type == "cuda":
-            from ..ops import kernels as K
-
-            img = self.wire.img[: self.n] if self.wire is not None else None
-            K.sgd_apply_multi(self.params, [s[: self.n] for s in srcs], self.lr, gscale=res.weight,
-                              momentum=self.cfg.momentum, wd=self.cfg.weight_decay, buf=self.momentum_buf,
-                              first=self._mom_first, n=self.n, img=img)
-        else:
-            if self.agg is None:
-                self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device)
-            self.agg.zero_()
-            for s in srcs:  # fixed order, fp32 accumulation
-                self.agg.add_(s[: self.n].to(torch.float32))
-            self.apply_range(self.agg, res.weight, 0, self.n)
+        self.update_range(srcs, res.weight, 0, self.n)
         self.finish_round_apply(self._time_end(t0))
         if buffers_sum is not None:
             self.set_buffers_from_sum(buffers_sum, len(members))
@@ -909,7 +589,7 @@ class ParameterServer:
         path = path or ckpt.path_for(self.cfg.ckpt_dir, step)
         ckpt.save(path, self.layout, self.arena, self.counters, step, self.cfg.mode, self.total_workers,
                   self._base_lr, self.momentum_buf, self.cfg.to_json(), dc_meansquare=self._dc_ms,
-                  adam=(self.adam_m, self.adam_v, self.adam_t) if self._adamw or self._lamb else None)
+                  adam=(self.adam_m, self.adam_v, self.adam_t) if self.rule.adam else None)
         self.log(f"[Checkpoint] global step {step} -> {path}")
         return path
 
@@ -940,7 +620,7 @@ class ParameterServer:
             self._dc_ms.copy_(ms.to(self.device))
         # AdamW / LAMB: both moments and the update count (absent, e.g. an SGD server's checkpoint:
         # zero moments, the next update is t = 1)
-        if self._adamw or self._lamb:
+        if self.rule.adam:
             st = obj.get("server_optimizer_state", {})
             if st.get("adam_m") is not None and st.get("adam_v") is not None:
                 self.adam_m.copy_(st["adam_m"].to(self.device))
@@ -959,20 +639,10 @@ class ParameterServer:
         m = self.core.metrics()
         m["update_time_source"] = self.update_time_source
         m["optimizer"] = self.cfg.optimizer
-        if self._lars:
-            m["lars_trust_ratio"] = self.lars_trust_ratios()
-        if self._adamw:
-            m["adamw"] = {"beta1": float(self.cfg.adam_beta1), "beta2": float(self.cfg.adam_beta2),
-                          "eps": float(self.cfg.adam_eps), "steps": int(self.adam_t)}
-        if self._lamb:
-            m["lamb"] = {"beta1": float(self.cfg.adam_beta1), "beta2": float(self.cfg.adam_beta2),
-                         "eps": float(self.cfg.adam_eps), "steps": int(self.adam_t)}
-            m["lamb_trust_ratio"] = self.lamb_trust_ratios()
+        m.update(self.rule.metrics(self))
         if int(getattr(self.cfg, "warmup_steps", 0) or 0) > 0:
             m["warmup_steps"] = int(self.cfg.warmup_steps)
             m["effective_lr"] = float(self.lr)
-        if self._guard:
-            m["gradient_guard"] = self.guard_counters()
         if self._dc:
             m["delay_compensation"] = {"lambda": float(self.cfg.dc_lambda), "adaptive": bool(self.cfg.dc_adaptive),
                                        "compensated_pushes": int(self.dc_compensated),

@@ -169,31 +169,18 @@ class ShardedSyncChannel(WatchedRounds):
 
     # ---- server side of this rank
     def apply_shard(self, weight: float, srcs: list):
-        """params[lo:hi] -= lr * weight * sum_r srcs[r] (fp32 sum in rank order), image range."""
+        """This rank's range of the round through the server's one entry (SGD: params[lo:hi] -= lr *
+        weight * sum_r srcs[r], fp32 sum in rank order; --optimizer adamw: this rank's slices of the
+        moments, every rank counts t itself), and the image of that range."""
         s = self.server
         n = self.hi - self.lo
         t0 = s._time_begin()
         if n > 0:
-            bf16_img = self.wire.img.dtype == torch.bfloat16
-            if s.device.type == "cuda":
-                from ..ops import kernels as K
-
-                buf = s.momentum_buf[self.lo:self.hi] if s.momentum_buf is not None else None
-                if s.cfg.optimizer == "adamw":  # this rank's slices of the moments; every rank counts t itself
-                    s._adamw_range([x[:n] for x in srcs], weight, self.lo, self.hi,
-                                   img=self.wire.img[self.lo:self.hi] if bf16_img else None)
-                else:
-                    K.sgd_apply_multi(s.params[self.lo:self.hi], [x[:n] for x in srcs], s.lr, gscale=weight,
-                                      momentum=s.cfg.momentum, wd=s.cfg.weight_decay, buf=buf, first=s._mom_first,
-                                      n=n, img=self.wire.img[self.lo:self.hi] if bf16_img else None)
-                if not bf16_img:
-                    self.wire.img[self.lo:self.hi].copy_(s.params[self.lo:self.hi])
-            else:
-                agg = torch.zeros(n, dtype=torch.float32, device=s.device)
-                for x in srcs:  # fixed order, fp32 accumulation
-                    agg.add_(x[:n].to(torch.float32))
-                s.apply_range(agg, weight, self.lo, self.hi)
-                self.wire.img[self.lo:self.hi].copy_(s.params[self.lo:self.hi])
+            img = self.wire.img[self.lo:self.hi]  # a bf16 image is written by the update itself
+            bf16_img = img.dtype == torch.bfloat16
+            s.update_range(srcs, weight, self.lo, self.hi, img=img if bf16_img else None)
+            if not bf16_img:
+                img.copy_(s.params[self.lo:self.hi])
         self.wire.publish_small(s.arena, self.rank)
         s.finish_round_apply(s._time_end(t0))
 

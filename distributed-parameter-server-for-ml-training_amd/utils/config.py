@@ -158,33 +158,18 @@ class PSConfig:
             raise ValueError(f"--topology must be colocated, dedicated or sharded, got {self.topology!r}")
         if self.optimizer not in ("sgd", "lars", "adamw", "lamb"):
             raise ValueError(f"--optimizer must be sgd, lars, adamw or lamb, got {self.optimizer!r}")
-        if self.optimizer == "adamw":
+        if self.optimizer in ("adamw", "lamb"):
+            opt = f"--optimizer {self.optimizer}"
             if not (0.0 <= self.adam_beta1 < 1.0) or not (0.0 <= self.adam_beta2 < 1.0):
-                raise ValueError("--optimizer adamw: --adam-beta1 and --adam-beta2 must be in [0, 1)")
+                raise ValueError(f"{opt}: --adam-beta1 and --adam-beta2 must be in [0, 1)")
             if not self.adam_eps > 0.0:
-                raise ValueError("--optimizer adamw: --adam-eps must be > 0")
+                raise ValueError(f"{opt}: --adam-eps must be > 0")
             if self.momentum:
-                raise ValueError("--optimizer adamw: --adam-beta1 is the momentum, --momentum must be 0")
-        if self.optimizer == "lamb":
-            if not (0.0 <= self.adam_beta1 < 1.0) or not (0.0 <= self.adam_beta2 < 1.0):
-                raise ValueError("--optimizer lamb: --adam-beta1 and --adam-beta2 must be in [0, 1)")
-            if not self.adam_eps > 0.0:
-                raise ValueError("--optimizer lamb: --adam-eps must be > 0")
-            if self.momentum:
-                raise ValueError("--optimizer lamb: --adam-beta1 is the momentum, --momentum must be 0")
-            if self.topology == "sharded":  # a shard boundary may split a tensor
-                raise ValueError("--optimizer lamb needs whole tensors on one server: not with --topology sharded")
-            if self.overlap is True:  # a gradient bucket may split a tensor
-                raise ValueError("--optimizer lamb updates the whole arena at once: not with --overlap")
+                raise ValueError(f"{opt}: --adam-beta1 is the momentum, --momentum must be 0")
         if int(self.warmup_steps) < 0:
             raise ValueError("--warmup-steps must be >= 0")
-        if self.optimizer == "lars":
-            if not (self.lars_trust > 0.0) or self.lars_eps < 0.0:
-                raise ValueError("--optimizer lars: --lars-trust must be > 0 and --lars-eps >= 0")
-            if self.topology == "sharded":  # a shard boundary may split a tensor
-                raise ValueError("--optimizer lars needs whole tensors on one server: not with --topology sharded")
-            if self.overlap is True:  # a gradient bucket may split a tensor
-                raise ValueError("--optimizer lars updates the whole arena at once: not with --overlap")
+        if self.optimizer == "lars" and (not (self.lars_trust > 0.0) or self.lars_eps < 0.0):
+            raise ValueError("--optimizer lars: --lars-trust must be > 0 and --lars-eps >= 0")
         if self.dc_lambda < 0.0:
             raise ValueError("--dc-lambda must be >= 0")
         if self.dc_adaptive and not self.dc_lambda > 0.0:
@@ -206,12 +191,18 @@ class PSConfig:
                                  f"{self.optimizer}")
             if self.dc_lambda > 0.0:
                 raise ValueError("--clip-norm / --skip-nonfinite run on the SGD server update: not with --dc-lambda")
-            if self.topology == "sharded":  # no shard sees the whole gradient
-                raise ValueError("--clip-norm / --skip-nonfinite need the whole gradient's norm on one server: "
-                                 "not with --topology sharded")
-            if self.overlap is True:  # a bucket is applied before the others have arrived
-                raise ValueError("--clip-norm / --skip-nonfinite need the whole gradient's norm before the first "
-                                 "parameter moves: not with --overlap")
+        if self.whole_arena_update:
+            # a shard boundary or a gradient bucket may split a tensor (lars, lamb); no shard sees the
+            # whole gradient, and a bucket is applied before the others have arrived (the guard)
+            who, one_server, at_once = (f"--optimizer {self.optimizer}", "needs whole tensors on one server",
+                                        "updates the whole arena at once")
+            if self.grad_guard:
+                who, one_server, at_once = ("--clip-norm / --skip-nonfinite", "need the whole gradient's norm on one "
+                                            "server", "need the whole gradient's norm before the first parameter moves")
+            if self.topology == "sharded":
+                raise ValueError(f"{who} {one_server}: not with --topology sharded")
+            if self.overlap is True:
+                raise ValueError(f"{who} {at_once}: not with --overlap")
         if self.topology == "sharded":  # parallel/sharded.py scope
             if self.mode != "sync" or self.codec not in ("fp16", "none") or self.bn_sync or self.ckpt_every \
                     or self.resume or max(1, self.sync_steps) != 1 or self.overlap is True:
@@ -249,15 +240,20 @@ class PSConfig:
     def resolve_overlap(self, world: int) -> bool:
         """--overlap / --no-overlap, or auto: bucketed rounds when there are peers to exchange
         with and the round qualifies (sync, one push per batch, dense wire, rank-0 server). The
-        error-feedback codecs (q8, topk) encode the whole gradient at once, and --optimizer lars
-        / lamb and the gradient guard (--clip-norm / --skip-nonfinite) need a norm of the whole gradient
-        before the first element moves: no bucketed rounds. --optimizer adamw is element-wise and
-        stays eligible."""
+        error-feedback codecs (q8, topk) encode the whole gradient at once, and a whole-arena update
+        (whole_arena_update) cannot start before the last bucket: no bucketed rounds. --optimizer
+        adamw is element-wise and stays eligible."""
         if self.overlap is None:
             self.overlap = (world > 1 and self.mode == "sync" and max(1, self.sync_steps) == 1
-                            and self.dense_wire and self.topology != "sharded"
-                            and self.optimizer not in ("lars", "lamb") and not self.grad_guard)
+                            and self.dense_wire and self.topology != "sharded" and not self.whole_arena_update)
         return bool(self.overlap)
+
+    @property
+    def whole_arena_update(self) -> bool:
+        """The server update needs a norm over the whole arena (every tensor's for --optimizer lars
+        / lamb, the whole gradient's for the gradient guard) before the first element moves: no
+        --topology sharded, no --overlap."""
+        return self.optimizer in ("lars", "lamb") or self.grad_guard
 
     @property
     def grad_guard(self) -> bool:
