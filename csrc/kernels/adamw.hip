@@ -17,25 +17,17 @@
 #include <math.h>
 
 #include "adamw_tail.hpp"
-#include "common.hpp"
+#include "wire.hpp"
 
 namespace psx {
 
-constexpr int kAdamwMaxSrc = 32;  // reference server.py:424-426 caps the job at 32 workers
-
-struct AdamwSrcs {
-  const void* p[kAdamwMaxSrc];
-  int n;
-};
-
-PSX_DEV float adamw_ld(const uint16_t* g, size_t i) { return (float)__builtin_bit_cast(_Float16, g[i]); }
-PSX_DEV float adamw_ld(const float* g, size_t i) { return g[i]; }
-
+// The two source loops below spell out wire_sum1 / wire_sum8 (wire.hpp): through the helpers both
+// kernels allocate two more VGPRs for the same arithmetic.
 template <typename GT>
-PSX_DEV void adamw_one(float* __restrict__ p, const AdamwSrcs& srcs, float* __restrict__ m, float* __restrict__ v,
+PSX_DEV void adamw_one(float* __restrict__ p, const WireSrcs& srcs, float* __restrict__ m, float* __restrict__ v,
                        size_t i, float gscale, const AdamwScalars& c, uint16_t* __restrict__ img) {
   float s = 0.f;
-  for (int k = 0; k < srcs.n; ++k) s += adamw_ld(reinterpret_cast<const GT*>(srcs.p[k]), i);
+  for (int k = 0; k < srcs.n; ++k) s += ld_wire(reinterpret_cast<const GT*>(srcs.p[k]), i);
   float mv = m[i], vv = v[i];
   const float nv = adamw_tail(s, p[i], mv, vv, gscale, c);
   p[i] = nv;
@@ -46,7 +38,7 @@ PSX_DEV void adamw_one(float* __restrict__ p, const AdamwSrcs& srcs, float* __re
 
 // element-wise form: any alignment
 template <typename GT>
-__global__ __launch_bounds__(256) void adamw_apply_kernel(float* __restrict__ p, AdamwSrcs srcs,
+__global__ __launch_bounds__(256) void adamw_apply_kernel(float* __restrict__ p, WireSrcs srcs,
                                                           float* __restrict__ m, float* __restrict__ v, size_t n,
                                                           float gscale, AdamwScalars c, uint16_t* __restrict__ img) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
@@ -56,7 +48,7 @@ __global__ __launch_bounds__(256) void adamw_apply_kernel(float* __restrict__ p,
 // vector form: scalar head [0, h), 8-element groups [h, h + 8 * ng), scalar tail up to n; every
 // pointer + h is 16-byte aligned (the host's choice of h)
 template <typename GT>
-__global__ __launch_bounds__(256) void adamw_apply_v8_kernel(float* __restrict__ p, AdamwSrcs srcs,
+__global__ __launch_bounds__(256) void adamw_apply_v8_kernel(float* __restrict__ p, WireSrcs srcs,
                                                              float* __restrict__ m, float* __restrict__ v, size_t n,
                                                              int h, float gscale, AdamwScalars c,
                                                              uint16_t* __restrict__ img) {
@@ -94,24 +86,13 @@ __global__ __launch_bounds__(256) void adamw_apply_v8_kernel(float* __restrict__
     st8(p + i, pv);
     st8(m + i, mv);
     st8(v + i, vv);
-    if (img) {
-      const u32x4 o = {pack_bf2(pv[0], pv[1]), pack_bf2(pv[2], pv[3]), pack_bf2(pv[4], pv[5]),
-                       pack_bf2(pv[6], pv[7])};
-      *reinterpret_cast<u32x4*>(img + i) = o;
-    }
+    if (img) st_bf8(img + i, pv);
   }
 }
 
 }  // namespace psx
 
 using namespace psx;
-
-static int adamw_grid(size_t work) {  // optim.hip's sizing: grid-stride loop, capped grid
-  size_t g = (work + 255) / 256;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
-}
 
 // the eight fp32 scalars of one update, each computed in double and rounded once
 static void adamw_scalars(double lr, double beta1, double beta2, double eps, double wd, long t, float out[8]) {
@@ -123,12 +104,6 @@ static void adamw_scalars(double lr, double beta1, double beta2, double eps, dou
   out[5] = (float)(1.0 / sqrt(1.0 - pow(beta2, (double)t)));
   out[6] = (float)eps;
   out[7] = (float)(1.0 - lr * wd);
-}
-
-// [a, a + na) and [b, b + nb) share a byte
-static bool adamw_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
 }
 
 extern "C" {
@@ -150,19 +125,13 @@ int psx_adamw_scalars(double lr, double beta1, double beta2, double eps, double 
 int psx_adamw_apply_multi(float* p, const void* const* srcs, int nsrc, int grad_fp16, float* m, float* v, long n,
                           double lr, float gscale, double beta1, double beta2, double eps, double wd, long t,
                           void* img, hipStream_t st) {
-  if (!p || !m || !v || !srcs || nsrc < 1 || nsrc > kAdamwMaxSrc || n <= 0 || t < 1)
-    return (int)hipErrorInvalidValue;
+  if (!p || !m || !v || n <= 0 || t < 1) return (int)hipErrorInvalidValue;
   const size_t esz = grad_fp16 ? 2 : 4, nb = (size_t)n * 4;
-  if (adamw_overlap(p, nb, m, nb) || adamw_overlap(p, nb, v, nb) || adamw_overlap(m, nb, v, nb))
+  if (ranges_overlap(p, nb, m, nb) || ranges_overlap(p, nb, v, nb) || ranges_overlap(m, nb, v, nb))
     return (int)hipErrorInvalidValue;
-  AdamwSrcs sl{};
-  sl.n = nsrc;
-  for (int k = 0; k < nsrc; ++k) {
-    const void* s = srcs[k];
-    if (!s || adamw_overlap(s, n * esz, p, nb) || adamw_overlap(s, n * esz, m, nb) || adamw_overlap(s, n * esz, v, nb))
-      return (int)hipErrorInvalidValue;
-    sl.p[k] = s;
-  }
+  WireSrcs sl{};
+  bool al = true;  // unused: the head search below decides the vector form
+  if (!fill_srcs(srcs, nsrc, esz, n, sl, al, nullptr, {p, m, v})) return (int)hipErrorInvalidValue;
   float sc[8];
   adamw_scalars(lr, beta1, beta2, eps, wd, t, sc);
   const AdamwScalars c{sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], sc[7]};
@@ -175,7 +144,7 @@ int psx_adamw_apply_multi(float* p, const void* const* srcs, int nsrc, int grad_
     if (ok) head = h;
   }
   if (head >= 0 && n - head >= 8) {
-    const int grid = adamw_grid((size_t)(n - head) >> 3);
+    const int grid = stream_grid((size_t)(n - head) >> 3);
     if (grad_fp16)
       hipLaunchKernelGGL(adamw_apply_v8_kernel<uint16_t>, dim3(grid), dim3(256), 0, st, p, sl, m, v, (size_t)n, head,
                          gscale, c, im);
@@ -184,7 +153,7 @@ int psx_adamw_apply_multi(float* p, const void* const* srcs, int nsrc, int grad_
                          gscale, c, im);
     return (int)hipGetLastError();
   }
-  const int grid = adamw_grid((size_t)n);
+  const int grid = stream_grid((size_t)n);
   if (grad_fp16)
     hipLaunchKernelGGL(adamw_apply_kernel<uint16_t>, dim3(grid), dim3(256), 0, st, p, sl, m, v, (size_t)n, gscale, c,
                        im);

@@ -24,31 +24,18 @@
 // No atomics, no LDS, no host synchronisation: both are plain stream work (graph-capturable).
 // The compensation is one device function (dc_grad) shared by every instantiation and by the
 // vector and scalar forms, so every path rounds the same way.
-#include "common.hpp"
-#include "sgd_tail.hpp"
+#include "wire.hpp"
 
 namespace psx {
-
-PSX_DEV float dc_ld(const uint16_t* g, size_t i) { return (float)__builtin_bit_cast(_Float16, g[i]); }
-PSX_DEV float dc_ld(const float* g, size_t i) { return g[i]; }
-
-// 8 consecutive gradient elements (one 16-byte fp16 load, or two fp32 ones)
-PSX_DEV void dc_ld8(const uint16_t* g, float (&v)[8]) {
-  const u32x4 w = *reinterpret_cast<const u32x4*>(g);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[2 * j] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w[j] & 0xffff));
-    v[2 * j + 1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w[j] >> 16));
-  }
-}
-PSX_DEV void dc_ld8(const float* g, float (&v)[8]) { ld8(g, v); }
 
 // The compensated gradient of one element, fp32, in the order of the header. msp: this element's
 // mean-square slot (read, then written; ADAPT only). comp = false: no backup, g~ = g.
 template <bool ADAPT>
 PSX_DEV float dc_grad(float g, float w, float bak, bool comp, float lam, float decay, float eps, float* msp) {
   if (ADAPT) {
-    const float m = decay * *msp + (1.f - decay) * g * g;
+    // the fma spelled out: left to contraction, the 8-per-lane form fused decay * ms into the add
+    // and the scalar form (a misaligned slice, the n % 8 tail) added two rounded products
+    const float m = __builtin_fmaf(decay, *msp, (1.f - decay) * g * g);
     *msp = m;
     lam = lam / sqrtf(m + eps);
   }
@@ -64,7 +51,7 @@ __global__ __launch_bounds__(256) void dc_apply_kernel(float* __restrict__ p, co
   const bool comp = bak != nullptr;
   auto one = [&](size_t i) {
     const float pv = p[i];
-    const float gc = dc_grad<ADAPT>(dc_ld(g, i), pv, comp ? bak[i] : pv, comp, lam, decay, eps, ms + i);
+    const float gc = dc_grad<ADAPT>(ld_wire(g, i), pv, comp ? bak[i] : pv, comp, lam, decay, eps, ms + i);
     const float nv = sgd_tail<MOM>(gc, pv, buf + i, lr, gscale, momentum, wd, first);
     p[i] = nv;
     if (img) img[i] = f2bf(nv);
@@ -79,7 +66,7 @@ __global__ __launch_bounds__(256) void dc_apply_kernel(float* __restrict__ p, co
   for (size_t q = tid; q < n8; q += nthr) {
     const size_t i = q << 3;
     float gv[8], pv[8], bk[8], mv[8], bv[8];
-    dc_ld8(g + i, gv);
+    ld_wire8(g + i, gv);
     ld8(p + i, pv);
     if (comp) ld8(bak + i, bk);
     if (ADAPT) ld8(ms + i, mv);
@@ -92,11 +79,7 @@ __global__ __launch_bounds__(256) void dc_apply_kernel(float* __restrict__ p, co
     st8(p + i, pv);
     if (ADAPT) st8(ms + i, mv);
     if (MOM) st8(buf + i, bv);
-    if (img) {
-      const u32x4 o = {pack_bf2(pv[0], pv[1]), pack_bf2(pv[2], pv[3]), pack_bf2(pv[4], pv[5]),
-                       pack_bf2(pv[6], pv[7])};
-      *reinterpret_cast<u32x4*>(img + i) = o;
-    }
+    if (img) st_bf8(img + i, pv);
   }
 }
 
@@ -133,15 +116,8 @@ __global__ __launch_bounds__(256) void dc_fetch_copy_kernel(const float* __restr
 
 using namespace psx;
 
-static bool dc_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // memory-bound: at most 2048 workgroups, grid-stride the rest
-static int dc_grid(size_t work) {
-  size_t g = (work + 255) / 256;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+static int dc_grid(size_t work) { return stream_grid(work, 2048); }
 
 extern "C" {
 
@@ -155,7 +131,7 @@ int psx_dc_apply(float* p, const void* g, const float* bak, float* ms, float* bu
   if (!p || !g || n <= 0) return (int)hipErrorInvalidValue;
   const bool mom = buf != nullptr && momentum != 0.f;
   const bool adapt = ms != nullptr;
-  const int vec = dc_al16(p) && dc_al16(g) && dc_al16(bak) && dc_al16(ms) && (!mom || dc_al16(buf)) && dc_al16(img);
+  const int vec = al16(p) && al16(g) && al16(bak) && al16(ms) && (!mom || al16(buf)) && al16(img);
   const int grid = dc_grid(vec ? ((size_t)n + 7) / 8 : (size_t)n);
   uint16_t* im = (uint16_t*)img;
 #define PSX_DC(G, M, A)                                                                                          \
@@ -181,7 +157,7 @@ int psx_dc_fetch_copy(const float* src, float* dst, float* bak, long n_arena, lo
   if (!src || !bak || n_params < 0 || n_params > n_arena) return (int)hipErrorInvalidValue;
   const size_t n = dst ? (size_t)n_arena : (size_t)n_params;  // backup only: nothing to read past it
   if (!n) return 0;
-  const int vec = dc_al16(src) && dc_al16(dst) && dc_al16(bak);
+  const int vec = al16(src) && al16(dst) && al16(bak);
   hipLaunchKernelGGL(dc_fetch_copy_kernel, dim3(dc_grid(vec ? (n + 3) / 4 : n)), dim3(256), 0, st, src, dst, bak, n,
                      (size_t)n_params, vec);
   return (int)hipGetLastError();

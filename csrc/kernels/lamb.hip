@@ -8,7 +8,7 @@
 // No clamp on |w| and no global gradient normalisation (the paper's optional phi(z) = min(max(z,
 // lo), hi) and pre-normalisation are left out).
 //
-// Two launches over the flat grid of (tensor, chunk of kLarsChunk elements) workgroups of
+// Two launches over the flat grid of (tensor, chunk of kChunk elements) workgroups of
 // lars_seg.hpp, on the caller's stream, no host synchronisation:
 //
 //   lamb_moments : s = sum_k decode(g_k) in fp32 in source order k = 0..W-1 (exactly the sum of
@@ -30,7 +30,6 @@
 // same bits.
 #include <math.h>
 
-#include "common.hpp"
 #include "lamb_tail.hpp"
 #include "lars_seg.hpp"
 
@@ -39,7 +38,7 @@ namespace psx {
 // GT: wire element (fp16 bits or fp32). DENSE: s is already in `stage` (no sources).
 // VEC: 16-byte accesses in the body (every base pointer 16-byte aligned).
 template <typename GT, bool DENSE, bool VEC>
-__global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restrict__ p, LarsSrcs srcs,
+__global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restrict__ p, WireSrcs srcs,
                                                            float* __restrict__ stage, float* __restrict__ m,
                                                            float* __restrict__ v, long n,
                                                            const LarsSeg* __restrict__ table, int ntensors,
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restri
   const int t = lars_find(table, ntensors, nblocks, &sh_t);
   if (t < 0) return;  // block-uniform
   const LarsSeg seg = table[t];
-  const LarsRange r = lars_range(seg, blockIdx.x - seg.first_block, n);
+  const ChunkRange r = chunk_range(seg.offset, seg.numel, blockIdx.x - seg.first_block, n);
   const int tid = threadIdx.x;
   const bool adapt = seg.adapt != 0;  // block-uniform
   float uu = 0.f, ww = 0.f;
@@ -61,42 +60,32 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restri
     ww = __builtin_fmaf(w, w, ww);
     return u;
   };
-  auto one = [&](long i) {
-    float s;
-    if constexpr (DENSE) {
-      s = stage[i];
-    } else {
-      s = 0.f;
-      for (int k = 0; k < srcs.n; ++k) s += lars_ld(reinterpret_cast<const GT*>(srcs.p[k]), i);
-    }
-    float mv = m[i], vv = v[i];
-    stage[i] = tail(s, p[i], mv, vv);
-    m[i] = mv;
-    v[i] = vv;
-  };
-  if (tid < r.ha - r.a0) one(r.a0 + tid);
-  const long ng = (r.tb - r.ha) >> 3;
-  for (long q = tid; q < ng; q += 256) {
-    const long i = r.ha + 8 * q;
-    if constexpr (VEC) {
-      float s[8], w[8], mv[8], vv[8];
-      if constexpr (DENSE) ld8(stage + i, s);
-      else lars_sum8<GT>(srcs, i, s);
-      ld8(p + i, w);
-      ld8(m + i, mv);
-      ld8(v + i, vv);
+  for_chunk<VEC>(
+      r,
+      [&](long i) {
+        float s;
+        if constexpr (DENSE) s = stage[i];
+        else s = wire_sum1<GT>(srcs, i);
+        float mv = m[i], vv = v[i];
+        stage[i] = tail(s, p[i], mv, vv);
+        m[i] = mv;
+        v[i] = vv;
+      },
+      [&](long i) {
+        float s[8], w[8], mv[8], vv[8];
+        if constexpr (DENSE) ld8(stage + i, s);
+        else wire_sum8<GT>(srcs, i, s);
+        ld8(p + i, w);
+        ld8(m + i, mv);
+        ld8(v + i, vv);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) s[j] = tail(s[j], w[j], mv[j], vv[j]);  // the scalar form's order
-      st8(stage + i, s);
-      st8(m + i, mv);
-      st8(v + i, vv);
-    } else {
-      for (int j = 0; j < 8; ++j) one(i + j);
-    }
-  }
-  if (tid < r.a1 - r.tb) one(r.tb + tid);
+        for (int j = 0; j < 8; ++j) s[j] = tail(s[j], w[j], mv[j], vv[j]);  // the scalar form's order
+        st8(stage + i, s);
+        st8(m + i, mv);
+        st8(v + i, vv);
+      });
   double duu = (double)uu, dww = (double)ww;
-  lars_block_sum2(duu, dww, red);
+  block_sum2_f64(duu, dww, red);
   if (tid == 0) {
     partials[2 * (long)blockIdx.x] = duu;
     partials[2 * (long)blockIdx.x + 1] = dww;
@@ -115,7 +104,7 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, 
   if (t < 0) return;  // block-uniform
   const LarsSeg seg = table[t];
   const int chunk = blockIdx.x - seg.first_block;
-  const LarsRange r = lars_range(seg, chunk, n);
+  const ChunkRange r = chunk_range(seg.offset, seg.numel, chunk, n);
   const int tid = threadIdx.x;
   float phi = 1.f;
   if (seg.adapt) {  // block-uniform
@@ -126,32 +115,22 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, 
   }
   if (chunk == 0 && tid == 0) ratios[t] = phi;
   const float step = lr * phi;
-  auto one = [&](long i) {
-    const float nv = lamb_step(p[i], stage[i], step);
-    p[i] = nv;
-    if (img) img[i] = f2bf(nv);
-  };
-  if (tid < r.ha - r.a0) one(r.a0 + tid);
-  const long ng = (r.tb - r.ha) >> 3;
-  for (long q = tid; q < ng; q += 256) {
-    const long i = r.ha + 8 * q;
-    if constexpr (VEC) {
-      float u[8], pv[8];
-      ld8(stage + i, u);
-      ld8(p + i, pv);
+  for_chunk<VEC>(
+      r,
+      [&](long i) {
+        const float nv = lamb_step(p[i], stage[i], step);
+        p[i] = nv;
+        if (img) img[i] = f2bf(nv);
+      },
+      [&](long i) {
+        float u[8], pv[8];
+        ld8(stage + i, u);
+        ld8(p + i, pv);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) pv[j] = lamb_step(pv[j], u[j], step);
-      st8(p + i, pv);
-      if (img) {
-        const u32x4 o = {pack_bf2(pv[0], pv[1]), pack_bf2(pv[2], pv[3]), pack_bf2(pv[4], pv[5]),
-                         pack_bf2(pv[6], pv[7])};
-        *reinterpret_cast<u32x4*>(img + i) = o;
-      }
-    } else {
-      for (int j = 0; j < 8; ++j) one(i + j);
-    }
-  }
-  if (tid < r.a1 - r.tb) one(r.tb + tid);
+        for (int j = 0; j < 8; ++j) pv[j] = lamb_step(pv[j], u[j], step);
+        st8(p + i, pv);
+        if (img) st_bf8(img + i, pv);
+      });
 }
 
 }  // namespace psx
@@ -159,14 +138,6 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, 
 using namespace psx;
 
 extern "C" int psx_adamw_scalars(double lr, double beta1, double beta2, double eps, double wd, long t, float* out);
-
-static bool lamb_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// [a, a + na) and [b, b + nb) share a byte
-static bool lamb_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
-}
 
 // the arguments both entries share; the four fp32 [n] buffers must be pairwise disjoint
 static bool lamb_args_ok(const void* p, const void* stage, const void* m, const void* v, long n, const void* table,
@@ -177,7 +148,7 @@ static bool lamb_args_ok(const void* p, const void* stage, const void* m, const 
   const size_t nb = (size_t)n * 4;
   for (int i = 0; i < 4; ++i)
     for (int j = i + 1; j < 4; ++j)
-      if (lamb_overlap(b[i], nb, b[j], nb)) return false;
+      if (ranges_overlap(b[i], nb, b[j], nb)) return false;
   return true;
 }
 
@@ -193,7 +164,7 @@ static int lamb_launch_apply(float* p, float* stage, long n, const void* table, 
                              double* partials, float* ratios, float lr, void* img, hipStream_t st) {
   const LarsSeg* tb = (const LarsSeg*)table;
   uint16_t* im = (uint16_t*)img;
-  if (lamb_al16(p) && lamb_al16(stage) && lamb_al16(img))
+  if (al16(p) && al16(stage) && al16(img))
     hipLaunchKernelGGL((lamb_apply_kernel<true>), dim3(nblocks), dim3(256), 0, st, p, (const float*)stage, n, tb,
                        ntensors, nblocks, (const double*)partials, ratios, lr, im);
   else
@@ -216,31 +187,17 @@ int psx_lamb_apply_multi(float* p, const void* const* srcs, int nsrc, int grad_f
                          long n, const void* table, int ntensors, int nblocks, double* partials, float* ratios,
                          float lr, float gscale, float wd, double beta1, double beta2, double eps, long t, void* img,
                          hipStream_t st) {
-  if (nsrc < 1 || nsrc > kLarsMaxSrc || !srcs) return (int)hipErrorInvalidValue;
   if (!lamb_args_ok(p, stage, m, v, n, table, ntensors, nblocks, partials, ratios, t)) return (int)hipErrorInvalidValue;
-  const size_t esz = grad_fp16 ? 2 : 4, nb = (size_t)n * 4;
-  LarsSrcs sl{};
-  sl.n = nsrc;
-  bool vec = lamb_al16(p) && lamb_al16(stage) && lamb_al16(m) && lamb_al16(v);
-  for (int k = 0; k < nsrc; ++k) {
-    const void* s = srcs[k];
-    if (!s || s == (const void*)stage || lamb_overlap(s, n * esz, p, nb) || lamb_overlap(s, n * esz, m, nb) ||
-        lamb_overlap(s, n * esz, v, nb))
-      return (int)hipErrorInvalidValue;
-    sl.p[k] = s;
-    vec = vec && lamb_al16(s);
-  }
+  WireSrcs sl{};
+  bool vec = al16(p) && al16(stage) && al16(m) && al16(v);
+  if (!fill_srcs(srcs, nsrc, grad_fp16 ? 2 : 4, n, sl, vec, stage, {p, m, v})) return (int)hipErrorInvalidValue;
   AdamwScalars c;
   if (lamb_scalars(beta1, beta2, eps, t, c)) return (int)hipErrorInvalidValue;
   const LarsSeg* tb = (const LarsSeg*)table;
-#define PSX_LM(G, V)                                                                                                 \
-  hipLaunchKernelGGL((lamb_moments_kernel<G, false, V>), dim3(nblocks), dim3(256), 0, st, (const float*)p, sl, stage, \
-                     m, v, n, tb, ntensors, nblocks, partials, gscale, wd, c)
-  if (grad_fp16 && vec) PSX_LM(uint16_t, true);
-  else if (grad_fp16) PSX_LM(uint16_t, false);
-  else if (vec) PSX_LM(float, true);
-  else PSX_LM(float, false);
-#undef PSX_LM
+  dispatch2(grad_fp16 != 0, vec, [&](auto H, auto V) {
+    hipLaunchKernelGGL((lamb_moments_kernel<wire_t<decltype(H)>, false, decltype(V)::value>), dim3(nblocks), dim3(256),
+                       0, st, (const float*)p, sl, stage, m, v, n, tb, ntensors, nblocks, partials, gscale, wd, c);
+  });
   const int rc = (int)hipGetLastError();
   if (rc) return rc;
   return lamb_launch_apply(p, stage, n, table, ntensors, nblocks, partials, ratios, lr, img, st);
@@ -254,9 +211,9 @@ int psx_lamb_apply(float* p, float* stage, float* m, float* v, long n, const voi
   if (!lamb_args_ok(p, stage, m, v, n, table, ntensors, nblocks, partials, ratios, t)) return (int)hipErrorInvalidValue;
   AdamwScalars c;
   if (lamb_scalars(beta1, beta2, eps, t, c)) return (int)hipErrorInvalidValue;
-  const LarsSrcs sl{};
+  const WireSrcs sl{};
   const LarsSeg* tb = (const LarsSeg*)table;
-  if (lamb_al16(p) && lamb_al16(stage) && lamb_al16(m) && lamb_al16(v))
+  if (al16(p) && al16(stage) && al16(m) && al16(v))
     hipLaunchKernelGGL((lamb_moments_kernel<float, true, true>), dim3(nblocks), dim3(256), 0, st, (const float*)p, sl,
                        stage, m, v, n, tb, ntensors, nblocks, partials, gscale, wd, c);
   else

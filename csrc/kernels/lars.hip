@@ -4,7 +4,7 @@
 // of floats. LARS scales every tensor's update by a trust ratio of two norms, so this file carries
 // the tensor boundaries of models/layout.py to the device (LarsSeg, one record per trainable
 // tensor; lars_seg.hpp, shared with lamb.hip) and reduces per tensor, in two launches over one
-// flat grid of (tensor, chunk of kLarsChunk elements) workgroups:
+// flat grid of (tensor, chunk of kChunk elements) workgroups:
 //
 //   lars_norms : s = sum_k decode(g_k) in fp32 in source order k = 0..W-1 (exactly the sum of
 //                sgd_apply_multi), written as fp32 to the staging buffer; one {sum s^2, sum w^2}
@@ -27,16 +27,14 @@
 // element: its head up to the next multiple of 8 arena elements and its tail are scalar accesses,
 // the body is 8 elements per lane (one 16-byte fp16 load per source, two 16-byte fp32 accesses) when
 // every base pointer is 16-byte aligned, and the same 8 elements with scalar accesses otherwise.
-#include "common.hpp"
 #include "lars_seg.hpp"
-#include "sgd_tail.hpp"
 
 namespace psx {
 
 // GT: wire element (fp16 bits or fp32). DENSE: s is already in `stage` (no sources, no rewrite).
 // VEC: 16-byte accesses in the body (every base pointer 16-byte aligned).
 template <typename GT, bool DENSE, bool VEC>
-__global__ __launch_bounds__(256) void lars_norms_kernel(const float* __restrict__ p, LarsSrcs srcs,
+__global__ __launch_bounds__(256) void lars_norms_kernel(const float* __restrict__ p, WireSrcs srcs,
                                                          float* __restrict__ stage, long n,
                                                          const LarsSeg* __restrict__ table, int ntensors, int nblocks,
                                                          double* __restrict__ partials) {
@@ -45,56 +43,40 @@ __global__ __launch_bounds__(256) void lars_norms_kernel(const float* __restrict
   const int t = lars_find(table, ntensors, nblocks, &sh_t);
   if (t < 0) return;  // block-uniform
   const LarsSeg seg = table[t];
-  const LarsRange r = lars_range(seg, blockIdx.x - seg.first_block, n);
+  const ChunkRange r = chunk_range(seg.offset, seg.numel, blockIdx.x - seg.first_block, n);
   const int tid = threadIdx.x;
   float ss = 0.f, ww = 0.f;
-  auto one = [&](long i) {
-    float s;
-    if constexpr (DENSE) {
-      s = stage[i];
-    } else {
-      s = 0.f;
-      for (int k = 0; k < srcs.n; ++k) s += lars_ld(reinterpret_cast<const GT*>(srcs.p[k]), i);
-      stage[i] = s;
-    }
-    const float w = p[i];
-    ss = __builtin_fmaf(s, s, ss);
-    ww = __builtin_fmaf(w, w, ww);
-  };
-  if (tid < r.ha - r.a0) one(r.a0 + tid);
-  const long ng = (r.tb - r.ha) >> 3;
-  for (long q = tid; q < ng; q += 256) {
-    const long i = r.ha + 8 * q;
-    if constexpr (VEC) {
-      float s[8];
-      if constexpr (DENSE) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(stage + i);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(stage + i + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          s[j] = a[j];
-          s[4 + j] = b[j];
+  for_chunk<VEC>(
+      r,
+      [&](long i) {
+        float s;
+        if constexpr (DENSE) {
+          s = stage[i];
+        } else {
+          s = wire_sum1<GT>(srcs, i);
+          stage[i] = s;
         }
-      } else {
-        lars_sum8<GT>(srcs, i, s);
-        *reinterpret_cast<f32x4*>(stage + i) = (f32x4){s[0], s[1], s[2], s[3]};
-        *reinterpret_cast<f32x4*>(stage + i + 4) = (f32x4){s[4], s[5], s[6], s[7]};
-      }
-      const f32x4 w0 = *reinterpret_cast<const f32x4*>(p + i);
-      const f32x4 w1 = *reinterpret_cast<const f32x4*>(p + i + 4);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {  // the scalar form's order: element by element
-        const float w = j < 4 ? w0[j] : w1[j - 4];
-        ss = __builtin_fmaf(s[j], s[j], ss);
+        const float w = p[i];
+        ss = __builtin_fmaf(s, s, ss);
         ww = __builtin_fmaf(w, w, ww);
-      }
-    } else {
-      for (int j = 0; j < 8; ++j) one(i + j);
-    }
-  }
-  if (tid < r.a1 - r.tb) one(r.tb + tid);
+      },
+      [&](long i) {
+        float s[8], w[8];
+        if constexpr (DENSE) {
+          ld8(stage + i, s);
+        } else {
+          wire_sum8<GT>(srcs, i, s);
+          st8(stage + i, s);
+        }
+        ld8(p + i, w);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {  // the scalar form's order: element by element
+          ss = __builtin_fmaf(s[j], s[j], ss);
+          ww = __builtin_fmaf(w[j], w[j], ww);
+        }
+      });
   double dss = (double)ss, dww = (double)ww;
-  lars_block_sum2(dss, dww, red);
+  block_sum2_f64(dss, dww, red);
   if (tid == 0) {
     partials[2 * (long)blockIdx.x] = dss;
     partials[2 * (long)blockIdx.x + 1] = dww;
@@ -115,7 +97,7 @@ __global__ __launch_bounds__(256) void lars_apply_kernel(float* __restrict__ p, 
   if (t < 0) return;  // block-uniform
   const LarsSeg seg = table[t];
   const int chunk = blockIdx.x - seg.first_block;
-  const LarsRange r = lars_range(seg, chunk, n);
+  const ChunkRange r = chunk_range(seg.offset, seg.numel, chunk, n);
   const int tid = threadIdx.x;
   float lam = 1.f, gs = gscale, wdl = 0.f;
   if (seg.adapt) {  // block-uniform
@@ -127,42 +109,12 @@ __global__ __launch_bounds__(256) void lars_apply_kernel(float* __restrict__ p, 
     wdl = lam * wd;
   }
   if (chunk == 0 && tid == 0) ratios[t] = lam;
-  auto one = [&](long i) {
-    const float pv = p[i];
-    const float nv = sgd_tail<MOM>(stage[i], pv, buf + i, lr, gs, momentum, wdl, first);
-    p[i] = nv;
-    if (img) img[i] = f2bf(nv);
-  };
-  if (tid < r.ha - r.a0) one(r.a0 + tid);
-  const long ng = (r.tb - r.ha) >> 3;
-  for (long q = tid; q < ng; q += 256) {
-    const long i = r.ha + 8 * q;
-    if constexpr (VEC) {
-      float s[8], pv[8], bv[8];
-      ld8(stage + i, s);
-      ld8(p + i, pv);
-      if (MOM && !first) ld8(buf + i, bv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pv[j] = sgd_tail<MOM>(s[j], pv[j], &bv[j], lr, gs, momentum, wdl, first);
-      st8(p + i, pv);
-      if (MOM) st8(buf + i, bv);
-      if (img) {
-        const u32x4 o = {pack_bf2(pv[0], pv[1]), pack_bf2(pv[2], pv[3]), pack_bf2(pv[4], pv[5]),
-                         pack_bf2(pv[6], pv[7])};
-        *reinterpret_cast<u32x4*>(img + i) = o;
-      }
-    } else {
-      for (int j = 0; j < 8; ++j) one(i + j);
-    }
-  }
-  if (tid < r.a1 - r.tb) one(r.tb + tid);
+  sgd_stage_chunk<MOM, VEC>(r, p, stage, buf, lr, gs, momentum, wdl, first, img);
 }
 
 }  // namespace psx
 
 using namespace psx;
-
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 static int lars_launch_apply(float* p, float* stage, float* buf, long n, const void* table, int ntensors, int nblocks,
                              double* partials, float* ratios, float lr, float gscale, float momentum, float wd,
@@ -171,15 +123,11 @@ static int lars_launch_apply(float* p, float* stage, float* buf, long n, const v
   const bool vec = al16(p) && al16(stage) && (!mom || al16(buf)) && al16(img);
   const LarsSeg* tb = (const LarsSeg*)table;
   uint16_t* im = (uint16_t*)img;
-#define PSX_LA(M, V)                                                                                             \
-  hipLaunchKernelGGL((lars_apply_kernel<M, V>), dim3(nblocks), dim3(256), 0, st, p, (const float*)stage, buf, n, \
-                     tb, ntensors, nblocks, (const double*)partials, ratios, lr, gscale, momentum, wd, trust,    \
-                     eps, first, im)
-  if (mom && vec) PSX_LA(true, true);
-  else if (mom) PSX_LA(true, false);
-  else if (vec) PSX_LA(false, true);
-  else PSX_LA(false, false);
-#undef PSX_LA
+  dispatch2(mom, vec, [&](auto M, auto V) {
+    hipLaunchKernelGGL((lars_apply_kernel<decltype(M)::value, decltype(V)::value>), dim3(nblocks), dim3(256), 0, st, p,
+                       (const float*)stage, buf, n, tb, ntensors, nblocks, (const double*)partials, ratios, lr, gscale,
+                       momentum, wd, trust, eps, first, im);
+  });
   return (int)hipGetLastError();
 }
 
@@ -191,7 +139,7 @@ static bool lars_args_ok(const void* p, const void* stage, long n, const void* t
 extern "C" {
 
 int psx_lars_table_size() { return (int)sizeof(LarsSeg); }
-int psx_lars_chunk() { return kLarsChunk; }
+int psx_lars_chunk() { return kChunk; }
 
 // The LARS update from nsrc gathered gradient wires (host array of nsrc <= 32 device pointers, all
 // fp16 or all fp32, >= n elements each): two launches on `st`, no host synchronisation.
@@ -204,25 +152,15 @@ int psx_lars_apply_multi(float* p, const void* const* srcs, int nsrc, int grad_f
                          const void* table, int ntensors, int nblocks, double* partials, float* ratios, float lr,
                          float gscale, float momentum, float wd, float trust, float eps, int first, void* img,
                          hipStream_t st) {
-  if (nsrc < 1 || nsrc > kLarsMaxSrc || !srcs) return (int)hipErrorInvalidValue;
   if (!lars_args_ok(p, stage, n, table, ntensors, nblocks, partials, ratios)) return (int)hipErrorInvalidValue;
-  LarsSrcs sl{};
-  sl.n = nsrc;
+  WireSrcs sl{};
   bool vec = al16(p) && al16(stage);
-  for (int k = 0; k < nsrc; ++k) {
-    if (!srcs[k] || srcs[k] == (const void*)stage) return (int)hipErrorInvalidValue;
-    sl.p[k] = srcs[k];
-    vec = vec && al16(srcs[k]);
-  }
+  if (!fill_srcs(srcs, nsrc, grad_fp16 ? 2 : 4, n, sl, vec, stage)) return (int)hipErrorInvalidValue;
   const LarsSeg* tb = (const LarsSeg*)table;
-#define PSX_LN(G, V)                                                                                              \
-  hipLaunchKernelGGL((lars_norms_kernel<G, false, V>), dim3(nblocks), dim3(256), 0, st, (const float*)p, sl, stage, \
-                     n, tb, ntensors, nblocks, partials)
-  if (grad_fp16 && vec) PSX_LN(uint16_t, true);
-  else if (grad_fp16) PSX_LN(uint16_t, false);
-  else if (vec) PSX_LN(float, true);
-  else PSX_LN(float, false);
-#undef PSX_LN
+  dispatch2(grad_fp16 != 0, vec, [&](auto H, auto V) {
+    hipLaunchKernelGGL((lars_norms_kernel<wire_t<decltype(H)>, false, decltype(V)::value>), dim3(nblocks), dim3(256), 0,
+                       st, (const float*)p, sl, stage, n, tb, ntensors, nblocks, partials);
+  });
   const int rc = (int)hipGetLastError();
   if (rc) return rc;
   return lars_launch_apply(p, stage, buf, n, table, ntensors, nblocks, partials, ratios, lr, gscale, momentum, wd,
@@ -235,7 +173,7 @@ int psx_lars_apply(float* p, float* stage, float* buf, long n, const void* table
                    double* partials, float* ratios, float lr, float gscale, float momentum, float wd, float trust,
                    float eps, int first, void* img, hipStream_t st) {
   if (!lars_args_ok(p, stage, n, table, ntensors, nblocks, partials, ratios)) return (int)hipErrorInvalidValue;
-  const LarsSrcs sl{};
+  const WireSrcs sl{};
   const LarsSeg* tb = (const LarsSeg*)table;
   if (al16(p) && al16(stage))
     hipLaunchKernelGGL((lars_norms_kernel<float, true, true>), dim3(nblocks), dim3(256), 0, st, (const float*)p, sl,

@@ -10,13 +10,9 @@
 //   * param_unpack  : fp32 OIHW master weights -> bf16 implicit-GEMM operands (KRSC for the
 //                     forward conv, transposed CRSK for the data-gradient conv); one launch for
 //                     every conv of the model, table-driven.
-#include "common.hpp"
-#include "sgd_tail.hpp"
+#include "wire.hpp"
 
 namespace psx {
-
-PSX_DEV float ld_grad(const uint16_t* g, size_t i) { return (float)__builtin_bit_cast(_Float16, g[i]); }
-PSX_DEV float ld_grad(const float* g, size_t i) { return g[i]; }
 
 // fp16 bits of an fp32 value, round to nearest even. The empty asm makes t a value of its own:
 // without it the compiler folds the fp32 multiply that produced t into v_fma_mixlo_f16, which
@@ -37,7 +33,7 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
                                                         uint16_t* __restrict__ img) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const float pv = p[i];
-    const float nv = sgd_tail<MOM>(ld_grad(g, i), pv, buf + i, lr, gscale, momentum, wd, first);
+    const float nv = sgd_tail<MOM>(ld_wire(g, i), pv, buf + i, lr, gscale, momentum, wd, first);
     p[i] = nv;
     if (img) img[i] = f2bf(nv);
   }
@@ -52,7 +48,7 @@ __global__ __launch_bounds__(256) void sgd_apply_h8_kernel(float* __restrict__ p
   const size_t n8 = n >> 3;
   if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {  // tail (n % 8 elements)
     const size_t i = (n8 << 3) + threadIdx.x;
-    const float nv = sgd_tail<false>(ld_grad(g, i), p[i], nullptr, lr, gscale, 0.f, wd, 0);
+    const float nv = sgd_tail<false>(ld_wire(g, i), p[i], nullptr, lr, gscale, 0.f, wd, 0);
     p[i] = nv;
     if (IMG) img[i] = f2bf(nv);
   }
@@ -87,21 +83,14 @@ __global__ __launch_bounds__(256) void sgd_apply_h8_kernel(float* __restrict__ p
 //   p <- p - lr * (gscale * sum_k decode(g_k) [+ wd p]) [momentum], gscale = 1/W,
 // every wire decoded to fp32 and summed in fp32 in the fixed source order k = 0..W-1 (what the
 // reference's numpy loop does; an RCCL fp16 reduce would round the running sum to fp16 at every
-// hop). One pass over the W wires + the parameters; img (optional) receives the bf16 image.
-constexpr int kMaxSrc = 32;  // reference server.py:424-426 caps the job at 32 workers
-struct SrcList {
-  const void* p[kMaxSrc];
-  int n;
-};
-
+// hop; wire.hpp). One pass over the W wires + the parameters; img (optional) receives the bf16 image.
 template <typename GT, bool MOM>
-__global__ __launch_bounds__(256) void sgd_apply_multi_kernel(float* __restrict__ p, SrcList srcs,
+__global__ __launch_bounds__(256) void sgd_apply_multi_kernel(float* __restrict__ p, WireSrcs srcs,
                                                               float* __restrict__ buf, size_t n, float lr,
                                                               float gscale, float momentum, float wd, int first,
                                                               uint16_t* __restrict__ img) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    float s = 0.f;
-    for (int k = 0; k < srcs.n; ++k) s += ld_grad(reinterpret_cast<const GT*>(srcs.p[k]), i);
+    const float s = wire_sum1<GT>(srcs, i);
     const float pv = p[i];
     const float nv = sgd_tail<MOM>(s, pv, buf + i, lr, gscale, momentum, wd, first);
     p[i] = nv;
@@ -113,27 +102,19 @@ __global__ __launch_bounds__(256) void sgd_apply_multi_kernel(float* __restrict_
 // 16-byte chunk loaded before the fixed-order sum
 // (same arithmetic as sgd_apply_multi_kernel: sgd_tail on the fp32 sum)
 template <bool IMG>
-__global__ __launch_bounds__(256) void sgd_apply_multi_h8_kernel(float* __restrict__ p, SrcList srcs, size_t n,
+__global__ __launch_bounds__(256) void sgd_apply_multi_h8_kernel(float* __restrict__ p, WireSrcs srcs, size_t n,
                                                                  float lr, float gscale, uint16_t* __restrict__ img) {
   const size_t n8 = n >> 3;
   if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {  // tail (n % 8 elements)
     const size_t i = (n8 << 3) + threadIdx.x;
-    float s = 0.f;
-    for (int k = 0; k < srcs.n; ++k) s += ld_grad(reinterpret_cast<const uint16_t*>(srcs.p[k]), i);
+    const float s = wire_sum1<uint16_t>(srcs, i);
     const float nv = sgd_tail<false>(s, p[i], nullptr, lr, gscale, 0.f, 0.f, 0);
     p[i] = nv;
     if (IMG) img[i] = f2bf(nv);
   }
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
-    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < srcs.n; ++k) {
-      const u32x4 gv = reinterpret_cast<const u32x4*>(srcs.p[k])[i];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s[2 * j] += (float)__builtin_bit_cast(_Float16, (uint16_t)(gv[j] & 0xffff));
-        s[2 * j + 1] += (float)__builtin_bit_cast(_Float16, (uint16_t)(gv[j] >> 16));
-      }
-    }
+    float s[8];
+    wire_sum8<uint16_t>(srcs, i << 3, s);
     f32x4 p0 = reinterpret_cast<f32x4*>(p)[2 * i];
     f32x4 p1 = reinterpret_cast<f32x4*>(p)[2 * i + 1];
 #pragma unroll
@@ -157,10 +138,10 @@ __global__ __launch_bounds__(256) void aggregate_kernel(const ST* const* __restr
                                                         DT* __restrict__ dst, size_t n, float scale, int accumulate) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     float s = 0.f;
-    for (int k = 0; k < nsrc; ++k) s += ld_grad(srcs[k], i);
+    for (int k = 0; k < nsrc; ++k) s += ld_wire(srcs[k], i);
     s *= scale;
     if constexpr (sizeof(DT) == 2) {
-      if (accumulate) s += ld_grad(dst, i);
+      if (accumulate) s += ld_wire(dst, i);
       dst[i] = f2h(s);
     } else {
       if (accumulate) s += dst[i];
@@ -359,13 +340,6 @@ __global__ __launch_bounds__(256) void param_unpack_kernel(const float* __restri
 
 using namespace psx;
 
-static int grid_for(size_t n) {
-  size_t g = (n + 255) / 256;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 extern "C" {
 
 // p -= lr * (gscale*g + wd*p) [with momentum buffer]; grads fp16 (wire) or fp32.
@@ -377,14 +351,14 @@ int psx_sgd_apply(float* p, const void* g, float* buf, long n, float lr, float g
   if (!mom && grad_fp16 && n >= 8 && ((uintptr_t)p % 32 == 0) && ((uintptr_t)g % 16 == 0) &&
       ((uintptr_t)img % 16 == 0)) {
     if (im)
-      hipLaunchKernelGGL(sgd_apply_h8_kernel<true>, dim3(grid_for(n / 8)), dim3(256), 0, st, p, (const uint16_t*)g,
+      hipLaunchKernelGGL(sgd_apply_h8_kernel<true>, dim3(stream_grid(n / 8)), dim3(256), 0, st, p, (const uint16_t*)g,
                          (size_t)n, lr, gscale, wd, im);
     else
-      hipLaunchKernelGGL(sgd_apply_h8_kernel<false>, dim3(grid_for(n / 8)), dim3(256), 0, st, p, (const uint16_t*)g,
+      hipLaunchKernelGGL(sgd_apply_h8_kernel<false>, dim3(stream_grid(n / 8)), dim3(256), 0, st, p, (const uint16_t*)g,
                          (size_t)n, lr, gscale, wd, im);
     return (int)hipGetLastError();
   }
-  const int grid = grid_for(n);
+  const int grid = stream_grid(n);
   if (grad_fp16) {
     if (mom)
       hipLaunchKernelGGL((sgd_apply_kernel<uint16_t, true>), dim3(grid), dim3(256), 0, st, p, (const uint16_t*)g, buf,
@@ -409,7 +383,7 @@ int psx_sgd_apply(float* p, const void* g, float* buf, long n, float lr, float g
 int psx_sgd_apply_multi(float* p, const void* const* srcs, int nsrc, float* buf, long n, float lr, float gscale,
                         float momentum, float wd, int first, int grad_fp16, void* img, hipStream_t st) {
   if (nsrc < 1 || nsrc > kMaxSrc) return (int)hipErrorInvalidValue;
-  SrcList sl{};
+  WireSrcs sl{};
   sl.n = nsrc;
   bool aligned = ((uintptr_t)p % 32 == 0) && ((uintptr_t)img % 16 == 0);
   for (int k = 0; k < nsrc; ++k) {
@@ -420,29 +394,25 @@ int psx_sgd_apply_multi(float* p, const void* const* srcs, int nsrc, float* buf,
   uint16_t* im = (uint16_t*)img;
   if (!mom && wd == 0.f && grad_fp16 && n >= 8 && aligned) {
     if (im)
-      hipLaunchKernelGGL(sgd_apply_multi_h8_kernel<true>, dim3(grid_for(n / 8)), dim3(256), 0, st, p, sl, (size_t)n,
+      hipLaunchKernelGGL(sgd_apply_multi_h8_kernel<true>, dim3(stream_grid(n / 8)), dim3(256), 0, st, p, sl, (size_t)n,
                          lr, gscale, im);
     else
-      hipLaunchKernelGGL(sgd_apply_multi_h8_kernel<false>, dim3(grid_for(n / 8)), dim3(256), 0, st, p, sl, (size_t)n,
+      hipLaunchKernelGGL(sgd_apply_multi_h8_kernel<false>, dim3(stream_grid(n / 8)), dim3(256), 0, st, p, sl, (size_t)n,
                          lr, gscale, im);
     return (int)hipGetLastError();
   }
-  const int grid = grid_for(n);
-#define PSX_SAM(G, M)                                                                                              \
-  hipLaunchKernelGGL((sgd_apply_multi_kernel<G, M>), dim3(grid), dim3(256), 0, st, p, sl, buf, (size_t)n, lr, gscale, \
-                     momentum, wd, first, im)
-  if (grad_fp16 && mom) PSX_SAM(uint16_t, true);
-  else if (grad_fp16) PSX_SAM(uint16_t, false);
-  else if (mom) PSX_SAM(float, true);
-  else PSX_SAM(float, false);
-#undef PSX_SAM
+  const int grid = stream_grid(n);
+  dispatch2(grad_fp16 != 0, mom, [&](auto H, auto M) {
+    hipLaunchKernelGGL((sgd_apply_multi_kernel<wire_t<decltype(H)>, decltype(M)::value>), dim3(grid), dim3(256), 0, st, p,
+                       sl, buf, (size_t)n, lr, gscale, momentum, wd, first, im);
+  });
   return (int)hipGetLastError();
 }
 
 // srcs: device array of nsrc device pointers.
 int psx_grad_aggregate(const void* const* srcs, int nsrc, int src_fp16, void* dst, int dst_fp16, long n, float scale,
                        int accumulate, hipStream_t st) {
-  const int grid = grid_for(n);
+  const int grid = stream_grid(n);
 #define PSX_AGG(S, D)                                                                                      \
   hipLaunchKernelGGL((aggregate_kernel<S, D>), dim3(grid), dim3(256), 0, st, (const S* const*)srcs, nsrc, \
                      (D*)dst, (size_t)n, scale, accumulate)
@@ -455,12 +425,12 @@ int psx_grad_aggregate(const void* const* srcs, int nsrc, int src_fp16, void* ds
 }
 
 int psx_fp16_pack(const float* src, void* dst, long n, float scale, hipStream_t st) {
-  hipLaunchKernelGGL(fp16_pack_kernel, dim3(grid_for(n)), dim3(256), 0, st, src, (uint16_t*)dst, (size_t)n, scale);
+  hipLaunchKernelGGL(fp16_pack_kernel, dim3(stream_grid(n)), dim3(256), 0, st, src, (uint16_t*)dst, (size_t)n, scale);
   return (int)hipGetLastError();
 }
 
 int psx_fp16_unpack(const void* src, float* dst, long n, float scale, hipStream_t st) {
-  hipLaunchKernelGGL(fp16_unpack_kernel, dim3(grid_for(n)), dim3(256), 0, st, (const uint16_t*)src, dst, (size_t)n,
+  hipLaunchKernelGGL(fp16_unpack_kernel, dim3(stream_grid(n)), dim3(256), 0, st, (const uint16_t*)src, dst, (size_t)n,
                      scale);
   return (int)hipGetLastError();
 }
@@ -503,7 +473,7 @@ int psx_unpack_desc_size() { return (int)sizeof(UnpackDesc); }
 // (parallel/codec.py WeightWire.small) for the native server loop (csrc/server/event_loop.cpp).
 int psx_gather_f32(const float* src, const long* idx, long n, float* dst, hipStream_t st) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(gather_f32_kernel, dim3(grid_for(n)), dim3(256), 0, st, src, idx, (size_t)n, dst);
+  hipLaunchKernelGGL(gather_f32_kernel, dim3(stream_grid(n)), dim3(256), 0, st, src, idx, (size_t)n, dst);
   return (int)hipGetLastError();
 }
 

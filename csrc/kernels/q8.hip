@@ -26,8 +26,7 @@
 //   * q8_decode      : dst = [dst +] scale * deq (in-process accumulation, reference semantics)
 #include <float.h>
 
-#include "common.hpp"
-#include "sgd_tail.hpp"
+#include "wire.hpp"
 
 // Everything below keeps its multiplies and adds apart (hipcc contracts by default); the shared
 // update tail above was parsed with the library default, as in optim.hip.
@@ -37,7 +36,6 @@ namespace psx {
 
 constexpr int kQ8Block = 256;
 constexpr int kQ8Magic = 0x31423851;  // the bytes 'Q' '8' 'B' '1'
-constexpr int kQ8MaxSrc = 32;
 
 struct Q8Layout {
   long nblk, scales_off, q_off, bytes;
@@ -135,7 +133,7 @@ __global__ __launch_bounds__(256) void q8_encode_kernel(const GT* __restrict__ g
 }
 
 struct Q8Srcs {
-  const uint8_t* p[kQ8MaxSrc];
+  const uint8_t* p[kMaxSrc];
   int n;
 };
 
@@ -287,13 +285,6 @@ __global__ __launch_bounds__(256) void q8_decode_kernel(const float* __restrict_
 
 using namespace psx;
 
-static int q8_grid(long work_items) {
-  long g = (work_items + 255) / 256;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 // [off, off + cnt) must start on a block and end on a block or at n
 static bool q8_range_ok(long n, long off, long cnt) {
   return n > 0 && n <= 0x7fffffffL && off >= 0 && cnt >= 0 && off % kQ8Block == 0 && off + cnt <= n &&
@@ -319,7 +310,7 @@ int psx_q8_encode(const void* g, int g_fp16, float* resid, long n, void* payload
   const long blk0 = off / kQ8Block, blk1 = (off + cnt + kQ8Block - 1) / kQ8Block;
   int* hdr = off == 0 ? (int*)pl : nullptr;
   const bool vec = (uintptr_t)resid % 16 == 0 && (uintptr_t)g % (g_fp16 ? 8 : 16) == 0;
-  const dim3 grid(q8_grid((blk1 - blk0) * 64));
+  const dim3 grid(stream_grid((blk1 - blk0) * 64));
 #define PSX_Q8E(G, V)                                                                                            \
   hipLaunchKernelGGL((q8_encode_kernel<G, V>), grid, dim3(256), 0, st, (const G*)g, resid, n, blk0, blk1, scales, \
                      qw, qwords, hdr)
@@ -337,7 +328,7 @@ int psx_q8_encode(const void* g, int g_fp16, float* resid, long n, void* payload
 // element 0 of the n-element arrays.
 int psx_q8_apply_multi(float* p, const void* const* payloads, int nsrc, float* buf, long n, long off, long cnt,
                        float lr, float gscale, float momentum, float wd, int first, void* img, hipStream_t st) {
-  if (nsrc < 1 || nsrc > kQ8MaxSrc || !q8_range_ok(n, off, cnt)) return (int)hipErrorInvalidValue;
+  if (nsrc < 1 || nsrc > kMaxSrc || !q8_range_ok(n, off, cnt)) return (int)hipErrorInvalidValue;
   if (cnt == 0) return 0;
   const Q8Layout l = q8_layout(n);
   Q8Srcs sl{};
@@ -351,7 +342,7 @@ int psx_q8_apply_multi(float* p, const void* const* payloads, int nsrc, float* b
   uint16_t* im = (uint16_t*)img;
   const long e0 = off, e1 = off + cnt;
   if (aligned && cnt >= 1024) {
-    const dim3 grid(q8_grid((cnt >> 10) * 64));
+    const dim3 grid(stream_grid((cnt >> 10) * 64));
 #define PSX_Q8A(M, I)                                                                                            \
   hipLaunchKernelGGL((q8_apply_multi_rows_kernel<M, I>), grid, dim3(256), 0, st, p, sl, l.q_off, buf, e0, e1, lr, \
                      gscale, momentum, wd, first, im)
@@ -362,7 +353,7 @@ int psx_q8_apply_multi(float* p, const void* const* payloads, int nsrc, float* b
 #undef PSX_Q8A
     return (int)hipGetLastError();
   }
-  const dim3 grid(q8_grid(cnt));
+  const dim3 grid(stream_grid(cnt));
   if (mom)
     hipLaunchKernelGGL(q8_apply_multi_kernel<true>, grid, dim3(256), 0, st, p, sl, l.q_off, buf, e0, e1, lr, gscale,
                        momentum, wd, first, im);
@@ -383,7 +374,7 @@ int psx_q8_decode(const void* payload, float* dst, long n, long off, long cnt, f
   const int8_t* q = (const int8_t*)(pl + l.q_off);
   const long e0 = off, e1 = off + cnt;
   const bool vec = (uintptr_t)dst % 16 == 0 && cnt >= 16;
-  const dim3 grid(q8_grid(vec ? cnt / 16 : cnt));
+  const dim3 grid(stream_grid(vec ? cnt / 16 : cnt));
 #define PSX_Q8D(A, V) \
   hipLaunchKernelGGL((q8_decode_kernel<A, V>), grid, dim3(256), 0, st, scales, q, dst, e0, e1, scale)
   if (add && vec) PSX_Q8D(true, true);

@@ -260,8 +260,6 @@ int alloc_worker(PsxLoop* L, int w) {
   return 0;
 }
 
-// the fused SGD apply of one gradient with the core's weight (+ the bf16 image of the updated
-// state when the fetch payload carries it; the fp32 fetch never reads one)
 // the worker's backup buffer (delay compensation), allocated at its first fetch
 int alloc_backup(PsxLoop* L, int w) {
   if (L->bak[w]) return 0;
@@ -280,6 +278,8 @@ int fetch_backup(PsxLoop* L, int w, float* dst) {
   return 0;
 }
 
+// the fused SGD apply of one gradient with the core's weight (+ the bf16 image of the updated
+// state when the fetch payload carries it; the fp32 fetch never reads one)
 int apply(PsxLoop* L, const void* g, float weight, int wid) {
   read_timings(L, false);
   std::pair<hipEvent_t, hipEvent_t> tp{nullptr, nullptr};

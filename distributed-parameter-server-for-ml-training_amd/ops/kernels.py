@@ -607,7 +607,38 @@ def q8_decode(payload, dst, n=None, scale=1.0, add=False, off=0, cnt=None):
           "q8_decode")
 
 
-LARS_CHUNK = 8192  # kLarsChunk in csrc/kernels/lars_seg.hpp: elements per workgroup of the LARS / LAMB grid
+def _wire_srcs(srcs, n, dev, state, what):
+    """The checked host array of a round's gathered wires: 1..32 sources (kMaxSrc,
+    csrc/kernels/wire.hpp) of one dtype, fp16 or fp32, >= n elements each, on ``dev``, contiguous,
+    none starting where a tensor of ``state`` does. Returns (c_void_p array, fp16)."""
+    assert 1 <= len(srcs) <= 32, f"{what} sources"
+    dt = srcs[0].dtype
+    assert dt in (torch.float16, torch.float32), what
+    taken = {t.data_ptr() for t in state}
+    assert all(s.dtype == dt and s.numel() >= n and s.device == dev and s.is_contiguous()
+               and s.data_ptr() not in taken for s in srcs), what
+    return (C.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs]), dt == torch.float16
+
+
+def _stage_common(p, stage, owner, buf, img, n, what):
+    """The checks the staged updates share (LARS, LAMB, the guard): ``owner`` is the LarsTable or
+    GuardState sized for the update (``n`` elements on its device); p and stage fp32, buf fp32 and
+    img bf16 when given, all contiguous with >= n elements on that device. Returns n."""
+    n = owner.n if n is None else n
+    assert n == owner.n and p.dtype == torch.float32 and p.is_contiguous() and p.numel() >= n, f"{what} p"
+    assert p.device == owner.device and p.device.type == "cuda", f"{what} device"
+    assert stage.dtype == torch.float32 and stage.is_contiguous() and stage.numel() >= n and stage.device == p.device, \
+        f"{what} stage"
+    if buf is not None:
+        assert buf.dtype == torch.float32 and buf.is_contiguous() and buf.numel() >= n and buf.device == p.device, \
+            f"{what} buf"
+    if img is not None:
+        assert img.dtype == torch.bfloat16 and img.is_contiguous() and img.numel() >= n and img.device == p.device, \
+            f"{what} img"
+    return n
+
+
+LARS_CHUNK = 8192  # kChunk in csrc/kernels/wire.hpp: elements per workgroup of the LARS / LAMB grid
 _LARS_SEG = [("offset", "<i8"), ("numel", "<i8"), ("adapt", "<i4"), ("first_block", "<i4")]  # LarsSeg
 
 
@@ -656,19 +687,6 @@ def lars_table(layout, device) -> LarsTable:
     return LarsTable(layout, device)
 
 
-def _lars_common(p, stage, table, buf, img, n, what):
-    n = table.n if n is None else n
-    assert n == table.n and p.dtype == torch.float32 and p.is_contiguous() and p.numel() >= n, f"{what} p"
-    assert p.device == table.device and p.device.type == "cuda", f"{what} device"
-    assert stage.dtype == torch.float32 and stage.is_contiguous() and stage.numel() >= n and stage.device == p.device, \
-        f"{what} stage"
-    if buf is not None:
-        assert buf.dtype == torch.float32 and buf.numel() >= n and buf.device == p.device, f"{what} buf"
-    if img is not None:
-        assert img.dtype == torch.bfloat16 and img.numel() >= n and img.device == p.device, f"{what} img"
-    return n
-
-
 def lars_apply_multi(p, srcs, stage, table: LarsTable, lr, gscale=1.0, momentum=0.0, wd=0.0, trust=0.001, eps=1e-8,
                      buf=None, first=False, n=None, img=None):
     """The LARS server update from the W gathered wires (csrc/kernels/lars.hip): ``stage``
@@ -677,13 +695,8 @@ def lars_apply_multi(p, srcs, stage, table: LarsTable, lr, gscale=1.0, momentum=
     |p| / (gscale * |s| + wd * |p| + eps) (1 when a norm is 0), the 1-D ones with d = gscale * s;
     then v = first ? d : momentum * v + d, p -= lr * v. All sources fp16 or all fp32; at most 32.
     Two launches on the current stream, no host synchronisation."""
-    n = _lars_common(p, stage, table, buf, img, n, "lars_apply_multi")
-    assert 1 <= len(srcs) <= 32
-    fp16 = srcs[0].dtype == torch.float16
-    assert srcs[0].dtype in (torch.float16, torch.float32), "lars_apply_multi"
-    assert all(s.dtype == srcs[0].dtype and s.numel() >= n and s.device == p.device and s.is_contiguous()
-               and s.data_ptr() != stage.data_ptr() for s in srcs), "lars_apply_multi"
-    arr = (C.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
+    n = _stage_common(p, stage, table, buf, img, n, "lars_apply_multi")
+    arr, fp16 = _wire_srcs(srcs, n, p.device, (stage,), "lars_apply_multi")
     check(kernels().psx_lars_apply_multi(ptr(p), arr, len(srcs), int(fp16), ptr(stage), ptr(buf), n, ptr(table.dev),
                                          table.ntensors, table.nblocks, ptr(table.partials), ptr(table.ratios),
                                          float(lr), float(gscale), float(momentum), float(wd), float(trust),
@@ -694,7 +707,7 @@ def lars_apply(p, stage, table: LarsTable, lr, gscale=1.0, momentum=0.0, wd=0.0,
                first=False, n=None, img=None):
     """lars_apply_multi for a gradient sum that is already dense fp32 in ``stage`` (decoded q8 /
     top-k payloads, an accumulated round): norms only, no rewrite, then the same apply."""
-    n = _lars_common(p, stage, table, buf, img, n, "lars_apply")
+    n = _stage_common(p, stage, table, buf, img, n, "lars_apply")
     check(kernels().psx_lars_apply(ptr(p), ptr(stage), ptr(buf), n, ptr(table.dev), table.ntensors, table.nblocks,
                                    ptr(table.partials), ptr(table.ratios), float(lr), float(gscale), float(momentum),
                                    float(wd), float(trust), float(eps), int(first), ptr(img), stream_ptr()),
@@ -743,17 +756,11 @@ def adamw_apply_multi(p, srcs, m, v, lr, t, gscale=1.0, beta1=0.9, beta2=0.999, 
     for x, what in ((p, "p"), (m, "m"), (v, "v")):
         assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= n and x.device == dev, \
             f"adamw_apply_multi {what}"
-    assert 1 <= len(srcs) <= 32, "adamw_apply_multi sources"
-    assert srcs[0].dtype in (torch.float16, torch.float32), "adamw_apply_multi"
-    fp16 = srcs[0].dtype == torch.float16
-    state = {p.data_ptr(), m.data_ptr(), v.data_ptr()}
-    assert len(state) == 3, "adamw_apply_multi: p, m, v alias"
-    assert all(s.dtype == srcs[0].dtype and s.numel() >= n and s.device == dev and s.is_contiguous()
-               and s.data_ptr() not in state for s in srcs), "adamw_apply_multi"
+    assert len({p.data_ptr(), m.data_ptr(), v.data_ptr()}) == 3, "adamw_apply_multi: p, m, v alias"
+    arr, fp16 = _wire_srcs(srcs, n, dev, (p, m, v), "adamw_apply_multi")
     if img is not None:
         assert img.dtype == torch.bfloat16 and img.is_contiguous() and img.numel() >= n and img.device == dev, \
             "adamw_apply_multi img"
-    arr = (C.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
     check(kernels().psx_adamw_apply_multi(ptr(p), arr, len(srcs), int(fp16), ptr(m), ptr(v), n, float(lr),
                                           float(gscale), float(beta1), float(beta2), float(eps), float(wd), int(t),
                                           ptr(img), stream_ptr()), "adamw_apply_multi")
@@ -778,7 +785,7 @@ def lamb_scalars_host(t, beta1=0.9, beta2=0.999, eps=1e-8):
 
 
 def _lamb_common(p, stage, m, v, table, img, n, t, what):
-    n = _lars_common(p, stage, table, None, img, n, what)
+    n = _stage_common(p, stage, table, None, img, n, what)
     assert int(t) >= 1, f"{what} t"
     for x, nm in ((m, "m"), (v, "v")):
         assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= n and x.device == p.device, \
@@ -797,13 +804,7 @@ def lamb_apply_multi(p, srcs, stage, m, v, table: LarsTable, lr, t, gscale=1.0, 
     the ratios, ``img`` (bf16) the image of the updated parameters. All sources fp16 or all fp32;
     at most 32. Two launches on the current stream, no host synchronisation."""
     n = _lamb_common(p, stage, m, v, table, img, n, t, "lamb_apply_multi")
-    assert 1 <= len(srcs) <= 32, "lamb_apply_multi sources"
-    fp16 = srcs[0].dtype == torch.float16
-    assert srcs[0].dtype in (torch.float16, torch.float32), "lamb_apply_multi"
-    state = {p.data_ptr(), stage.data_ptr(), m.data_ptr(), v.data_ptr()}
-    assert all(s.dtype == srcs[0].dtype and s.numel() >= n and s.device == p.device and s.is_contiguous()
-               and s.data_ptr() not in state for s in srcs), "lamb_apply_multi"
-    arr = (C.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
+    arr, fp16 = _wire_srcs(srcs, n, p.device, (p, stage, m, v), "lamb_apply_multi")
     check(kernels().psx_lamb_apply_multi(ptr(p), arr, len(srcs), int(fp16), ptr(stage), ptr(m), ptr(v), n,
                                          ptr(table.dev), table.ntensors, table.nblocks, ptr(table.partials),
                                          ptr(table.ratios), float(lr), float(gscale), float(wd), float(beta1),
@@ -860,7 +861,7 @@ def dc_fetch_copy(src, dst, bak, n_params=None):
     check(kernels().psx_dc_fetch_copy(ptr(src), ptr(dst), ptr(bak), n_arena, n_params, stream_ptr()), "dc_fetch_copy")
 
 
-GUARD_CHUNK = 8192  # kGuardChunk in csrc/kernels/gguard.hip: elements per workgroup of the guard grid
+GUARD_CHUNK = 8192  # kChunk in csrc/kernels/wire.hpp: elements per workgroup of the guard grid
 _GUARD_STATE = [("S", "<f8"), ("norm", "<f8"), ("coef", "<f4"), ("skip", "<i4"), ("rounds", "<i8"),
                 ("clipped_rounds", "<i8"), ("skipped_rounds", "<i8"), ("norm_last", "<f8"), ("norm_max", "<f8"),
                 ("norm_sum", "<f8")]  # GuardState
@@ -896,17 +897,7 @@ class GuardState:
 
 
 def _guard_common(p, stage, state, buf, img, n, clip_norm, what):
-    n = state.n if n is None else n
-    assert n == state.n and p.dtype == torch.float32 and p.is_contiguous() and p.numel() >= n, f"{what} p"
-    assert p.device == state.device and p.device.type == "cuda", f"{what} device"
-    assert stage.dtype == torch.float32 and stage.is_contiguous() and stage.numel() >= n and stage.device == p.device, \
-        f"{what} stage"
-    if buf is not None:
-        assert buf.dtype == torch.float32 and buf.is_contiguous() and buf.numel() >= n and buf.device == p.device, \
-            f"{what} buf"
-    if img is not None:
-        assert img.dtype == torch.bfloat16 and img.is_contiguous() and img.numel() >= n and img.device == p.device, \
-            f"{what} img"
+    n = _stage_common(p, stage, state, buf, img, n, what)
     assert clip_norm >= 0.0, f"{what} clip_norm"
     return n
 
@@ -920,12 +911,7 @@ def guard_apply_multi(p, srcs, stage, state: GuardState, lr, gscale=1.0, momentu
     0). All sources fp16 or all fp32; at most 32. Three launches on the current stream, no host
     synchronisation; the decision and the counters are in ``state``."""
     n = _guard_common(p, stage, state, buf, img, n, clip_norm, "guard_apply_multi")
-    assert 1 <= len(srcs) <= 32
-    fp16 = srcs[0].dtype == torch.float16
-    assert srcs[0].dtype in (torch.float16, torch.float32), "guard_apply_multi"
-    assert all(s.dtype == srcs[0].dtype and s.numel() >= n and s.device == p.device and s.is_contiguous()
-               and s.data_ptr() != stage.data_ptr() for s in srcs), "guard_apply_multi"
-    arr = (C.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
+    arr, fp16 = _wire_srcs(srcs, n, p.device, (stage,), "guard_apply_multi")
     check(kernels().psx_guard_apply_multi(ptr(p), arr, len(srcs), int(fp16), ptr(stage), ptr(buf), n,
                                           ptr(state.partials), ptr(state.state), float(lr), float(gscale),
                                           float(momentum), float(wd), float(clip_norm), int(first), ptr(img),
