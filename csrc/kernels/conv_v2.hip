@@ -1,8 +1,12 @@
 // Implicit-GEMM convolution v2: LDS-DMA (global_load_lds) operand staging, 3-stage LDS ring
 // with counted vmcnt waits, optional split-K. Forward conv and data-gradient conv.
 //
-// Same math as conv_gemm.hip (v1) — see there for the GEMM formulation and the MFMA
-// orientation — but the mainloop is built for CDNA4 latency hiding:
+// The GEMM: out[oc][pix] = sum_k W[oc][k] * im2col(in)[pix][k], k = (tap, channel) with the channel
+// fastest (Kg columns, zero padded). Output channels are the MFMA's M rows (A operand = weight
+// rows), pixels its N columns (B operand = gathered pixel rows), both K-contiguous in LDS; a lane
+// of a 16x16 tile then holds 4 consecutive channels of pixel lane & 15 (mma_chunk, common.hpp),
+// which is what NHWC stores want. The data gradient is the same GEMM over dy against the
+// data-gradient weight rows [IC][Kg]. The mainloop is built for CDNA4 latency hiding:
 //   * operands go HBM/L2 -> LDS with `global_load_lds_dwordx4` (no VGPR staging). The im2col
 //     gather is expressed through the per-lane *source* address (any pixel / tap / channel
 //     chunk, zero padding = a pointer to a 16-byte zero page), while the LDS destination stays
@@ -17,28 +21,6 @@
 
 #include "bnfin.hpp"
 #include "pipeline.hpp"
-
-// fp32 register double buffer of the MFMA fragments (A/B builds: csrc/build.py --variant):
-// bit 0 the tap-reuse mainloop, bit 1 the generic one. Same-box A/B (fp32 layers, B=128, us
-// fwd/dgrad): tap reuse 32x32 102.2/96.7 -> 98.9/94.6, 8x8 89.7/87.9 -> 87.1/83.7, 4x4
-// 103.0/96.3 -> 92.9/89.5 (bench 5.15 -> 5.03 ms/step); the generic loop (stride 2, 1x1)
-// measured neutral to 4 % slower, so only bit 0 is on.
-#ifndef PSX_CONV_PF
-#define PSX_CONV_PF 1
-#endif
-// bf16: the same double buffer in the tap-reuse loop. Same-box A/B (bf16 layers, us fwd/dgrad):
-// 32x32 30.9/23.0 -> 25.5/22.0, 16x16 22.9/19.4 -> 18.9/17.3, 4x4 23.5/22.0 -> 21.1/19.7 (the
-// bf16 tile widths: tapr_bn)
-#ifndef PSX_CONV_PF_BF16
-#define PSX_CONV_PF_BF16 1
-#endif
-// epilogue rows whose global loads are issued together (A/B builds: -D PSX_EPI_U=1)
-#ifndef PSX_EPI_U
-#define PSX_EPI_U 4
-#endif
-#ifndef PSX_TAPR_F32_128
-#define PSX_TAPR_F32_128 1
-#endif
 
 namespace psx {
 
@@ -93,6 +75,12 @@ __constant__ float kWinoAT[4][6] = {{1.f, 1.f, 1.f, 1.f, 1.f, 0.f},
                                     {0.f, 1.f, -1.f, 8.f, -8.f, 1.f}};
 
 PSX_DEV int kmaj2(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
+
+// LDS bytes of conv2_kernel's mainloop, for the launchers and the kernel's own epilogue check:
+// the generic ring of (A | B) stages, and the tap-reuse loop's two stages of A0 A1 A2 | X
+// (TAPR = 2: 8 more window rows for the halo pixels and the zero slot)
+constexpr int ring_lds(int BM, int BN, int stages) { return stages * (BM + BN) * 128; }
+constexpr int tapr_lds(int BM, int BN, int TAPR) { return 2 * (3 * BM + (TAPR == 2 ? BN + 8 : BN)) * 128; }
 
 template <int MODE, typename T>
 PSX_DEV const T* gather_src(const Conv2Args& a, int nbase, int hb, int wb, bool pv, int gk) {
@@ -251,91 +239,63 @@ __global__ __launch_bounds__(256) void conv2_kernel(Conv2Args a) {
         boff[n][sx] = slot * 128 + ((fch ^ ((slot >> 1) & 7)) << 4);
       }
     }
-    if constexpr ((sizeof(T) == 4 || PSX_CONV_PF_BF16) && (PSX_CONV_PF & 1)) {
-      // Fragments are double-buffered in registers: a macro step is 6 sub-steps q = (tap sx = q/2,
-      // half kk = q%2), and the LDS reads of sub-step q+1 are issued before the MFMAs of q, so the
-      // read latency (one s_waitcnt lgkmcnt(0) in front of every sub-step's MFMAs before) hides
-      // behind them. At the last sub-step the stage boundary comes first — this wave's DMA of the
-      // next stage retired, its own reads of this stage retired (lgkmcnt), barrier, DMA of step t+2
-      // into the stage just drained, reads of the next stage's first sub-step — then its MFMAs.
-      auto load_frags = [&](const unsigned char* base, int q, u32x4(&fa)[MT], u32x4(&fb)[NT]) {
-        const int sx = q >> 1, kk = q & 1;
-        const unsigned char* A = base + sx * BM * 128;
-        const unsigned char* X = base + XOFF;
+    // Fragments are double-buffered in registers: a macro step is 6 sub-steps q = (tap sx = q/2,
+    // half kk = q%2), and the LDS reads of sub-step q+1 are issued before the MFMAs of q, so the
+    // read latency hides behind them. At the last sub-step the stage boundary comes first — this
+    // wave's DMA of the next stage retired, its own reads of this stage retired (lgkmcnt), barrier,
+    // DMA of step t+2 into the stage just drained, reads of the next stage's first sub-step — then
+    // its MFMAs. Against a single fragment set (one s_waitcnt lgkmcnt(0) in front of every
+    // sub-step's MFMAs), same box, B=128, us fwd/dgrad: fp32 32x32 102.2/96.7 -> 98.9/94.6, 8x8
+    // 89.7/87.9 -> 87.1/83.7, 4x4 103.0/96.3 -> 92.9/89.5 (bench 5.15 -> 5.03 ms/step); bf16 32x32
+    // 30.9/23.0 -> 25.5/22.0, 16x16 22.9/19.4 -> 18.9/17.3, 4x4 23.5/22.0 -> 21.1/19.7.
+    auto load_frags = [&](const unsigned char* base, int q, u32x4(&fa)[MT], u32x4(&fb)[NT]) {
+      const int sx = q >> 1, kk = q & 1;
+      const unsigned char* A = base + sx * BM * 128;
+      const unsigned char* X = base + XOFF;
 #pragma unroll
-        for (int m = 0; m < MT; ++m)
-          fa[m] = *reinterpret_cast<const u32x4*>(A + kmaj2(wm * (BM / WGM) + m * 16 + frow, kk * 4 + fch));
+      for (int m = 0; m < MT; ++m)
+        fa[m] = *reinterpret_cast<const u32x4*>(A + kmaj2(wm * (BM / WGM) + m * 16 + frow, kk * 4 + fch));
 #pragma unroll
-        for (int n = 0; n < NT; ++n) fb[n] = *reinterpret_cast<const u32x4*>(X + (boff[n][sx] ^ (kk << 6)));
-      };
-      u32x4 fa0[MT], fb0[NT], fa1[MT], fb1[NT];
-      if (HALO) __syncthreads();
-      if (nmac > 0) {
-        issue_t(0, 0);
-        wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (nmac > 1) issue_t(1, 1);
-        load_frags(smem, 0, fa0, fb0);
-      }
-      for (int t = 0; t < nmac; ++t) {
-        const unsigned char* base = smem + (t & 1) * TST;
-        auto sub = [&](auto qc, u32x4(&fa)[MT], u32x4(&fb)[NT], u32x4(&na)[MT], u32x4(&nb)[NT]) {
-          constexpr int q = decltype(qc)::value, sx = q >> 1;
-          if constexpr (q < 5) {
-            load_frags(base, q + 1, na, nb);
-          } else if (t + 1 < nmac) {
-            wait_vmcnt<0>();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            if (t + 2 < nmac) issue_t(t + 2, t & 1);
-            load_frags(smem + ((t + 1) & 1) * TST, 0, na, nb);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          if constexpr (!HALO && sx != 1) {
-#pragma unroll
-            for (int n = 0; n < NT; ++n)
-              if (!keep[n][sx]) fb[n] = u32x4{0u, 0u, 0u, 0u};
-          }
-          mma_tiles<MT, NT, T>(acc, fa, fb);
-        };
-        sub(std::integral_constant<int, 0>{}, fa0, fb0, fa1, fb1);
-        sub(std::integral_constant<int, 1>{}, fa1, fb1, fa0, fb0);
-        sub(std::integral_constant<int, 2>{}, fa0, fb0, fa1, fb1);
-        sub(std::integral_constant<int, 3>{}, fa1, fb1, fa0, fb0);
-        sub(std::integral_constant<int, 4>{}, fa0, fb0, fa1, fb1);
-        sub(std::integral_constant<int, 5>{}, fa1, fb1, fa0, fb0);
-      }
-    } else {
-      // single fragment set (PSX_CONV_PF_BF16=0 builds)
-      if (HALO) __syncthreads();
-      if (nmac > 0) issue_t(0, 0);
-      for (int t = 0; t < nmac; ++t) {
-        wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (t + 1 < nmac) issue_t(t + 1, (t + 1) & 1);
-        const unsigned char* base = smem + (t & 1) * TST;
-        const unsigned char* X = base + XOFF;
-#pragma unroll
-        for (int sx = 0; sx < 3; ++sx) {
-          const unsigned char* A = base + sx * BM * 128;
-#pragma unroll
-          for (int kk = 0; kk < 2; ++kk) {
-            u32x4 fa[MT], fb[NT];
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-              fa[m] = *reinterpret_cast<const u32x4*>(A + kmaj2(wm * (BM / WGM) + m * 16 + frow, kk * 4 + fch));
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-              fb[n] = *reinterpret_cast<const u32x4*>(X + (boff[n][sx] ^ (kk << 6)));
-              if (!HALO && sx != 1 && !keep[n][sx]) fb[n] = u32x4{0u, 0u, 0u, 0u};
-            }
-            mma_tiles<MT, NT, T>(acc, fa, fb);
-          }
+      for (int n = 0; n < NT; ++n) fb[n] = *reinterpret_cast<const u32x4*>(X + (boff[n][sx] ^ (kk << 6)));
+    };
+    u32x4 fa0[MT], fb0[NT], fa1[MT], fb1[NT];
+    if (HALO) __syncthreads();
+    if (nmac > 0) {
+      issue_t(0, 0);
+      wait_vmcnt<0>();
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if (nmac > 1) issue_t(1, 1);
+      load_frags(smem, 0, fa0, fb0);
+    }
+    for (int t = 0; t < nmac; ++t) {
+      const unsigned char* base = smem + (t & 1) * TST;
+      auto sub = [&](auto qc, u32x4(&fa)[MT], u32x4(&fb)[NT], u32x4(&na)[MT], u32x4(&nb)[NT]) {
+        constexpr int q = decltype(qc)::value, sx = q >> 1;
+        if constexpr (q < 5) {
+          load_frags(base, q + 1, na, nb);
+        } else if (t + 1 < nmac) {
+          wait_vmcnt<0>();
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_s_barrier();
+          asm volatile("" ::: "memory");
+          if (t + 2 < nmac) issue_t(t + 2, t & 1);
+          load_frags(smem + ((t + 1) & 1) * TST, 0, na, nb);
         }
-      }
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (!HALO && sx != 1) {
+#pragma unroll
+          for (int n = 0; n < NT; ++n)
+            if (!keep[n][sx]) fb[n] = u32x4{0u, 0u, 0u, 0u};
+        }
+        mma_tiles<MT, NT, T>(acc, fa, fb);
+      };
+      sub(std::integral_constant<int, 0>{}, fa0, fb0, fa1, fb1);
+      sub(std::integral_constant<int, 1>{}, fa1, fb1, fa0, fb0);
+      sub(std::integral_constant<int, 2>{}, fa0, fb0, fa1, fb1);
+      sub(std::integral_constant<int, 3>{}, fa1, fb1, fa0, fb0);
+      sub(std::integral_constant<int, 4>{}, fa0, fb0, fa1, fb1);
+      sub(std::integral_constant<int, 5>{}, fa1, fb1, fa0, fb0);
     }
   } else {
   // ---- per-lane DMA source state (fixed across k-steps) ----
@@ -359,11 +319,7 @@ __global__ __launch_bounds__(256) void conv2_kernel(Conv2Args a) {
   bool pv[LB];
   // a pure GEMM needs no (n, oh, ow) decomposition: two integer divisions (~70 VALU) per staged
   // row, which a one- or two-k-step 1x1 layer otherwise pays as much as its whole epilogue
-#ifdef PSX_NO_GEMM1X1  // A/B builds
-  const bool gemm1x1 = false;
-#else
   const bool gemm1x1 = (MODE == 0 || MODE == 1) && a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0;
-#endif
 #pragma unroll
   for (int i = 0; i < LB; ++i) {
     const int row = (i * 4 + wid) * 8 + lrow;
@@ -489,53 +445,14 @@ __global__ __launch_bounds__(256) void conv2_kernel(Conv2Args a) {
     for (int n = 0; n < NT; ++n)
       fb[n] = *reinterpret_cast<const u32x4*>(B + kmaj2(wn * (BN / WGN) + n * 16 + frow, kk * 4 + fch));
   };
-  if (a.nstg != 2) {
-    if (nk > 0) issue(0, 0);
-    if (nk > 1) issue(1, 1);
-  }
-  if constexpr (sizeof(T) == 4 && (PSX_CONV_PF & 2)) {
-    // fp32: the fragments of the next half k-step are read before the MFMAs of the current one
-    // (register double buffer, as in the tap-reuse loop); the stage boundary — DMA of k-step
-    // ks+1 retired, this wave's reads of stage ks retired, barrier, DMA of ks+3 into stage ks —
-    // sits between the two halves of k-step ks.
-    u32x4 fa0[MT], fb0[NT], fa1[MT], fb1[NT];
-    if (nk > 0) {
-      if (nk > 1)
-        wait_vmcnt<LA + LB>();
-      else
-        wait_vmcnt<0>();
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (nk > 2) issue(2, 2);
-      load_frags(0, 0, fa0, fb0);
-    }
-    int stage = 0;
-    for (int ks = 0; ks < nk; ++ks) {
-      const int nxt = stage == 2 ? 0 : stage + 1;
-      load_frags(stage, 1, fa1, fb1);
-      __builtin_amdgcn_sched_barrier(0);
-      mma_tiles<MT, NT, T>(acc, fa0, fb0);
-      if (ks + 1 < nk) {
-        if (ks + 2 < nk)
-          wait_vmcnt<LA + LB>();
-        else
-          wait_vmcnt<0>();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (ks + 3 < nk) issue(ks + 3, stage);
-        load_frags(nxt, 0, fa0, fb0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      mma_tiles<MT, NT, T>(acc, fa1, fb1);
-      stage = nxt;
-    }
-  } else if (a.nstg == 2) {
+  // (The register double buffer of the tap-reuse loop measured neutral to 4 % slower here, on the
+  // fp32 stride-2 and 1x1 layers, so both rings read a single fragment set per half k-step.)
+  if (a.nstg == 2) {
     // 2-deep ring: k-step ks + 1 is issued into the other stage once every wave has passed the
     // barrier, i.e. finished reading it (k-step ks - 1); its DMA overlaps k-step ks's MFMAs
     for (int ks = 0; ks < nk; ++ks) {
       const int stage = ks & 1;
-      if (ks == 0) issue(0, 0);  // (the shared prologue above issued nothing: nstg == 2 skips it)
+      if (ks == 0) issue(0, 0);
       wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
@@ -548,6 +465,8 @@ __global__ __launch_bounds__(256) void conv2_kernel(Conv2Args a) {
       }
     }
   } else {
+    if (nk > 0) issue(0, 0);
+    if (nk > 1) issue(1, 1);
     int stage = 0;
     for (int ks = 0; ks < nk; ++ks) {
       if (ks + 1 < nk)
@@ -592,8 +511,7 @@ __global__ __launch_bounds__(256) void conv2_kernel(Conv2Args a) {
     constexpr int TS = BM + 4;      // fp32 row stride of the staged tile (spreads the banks)
     constexpr int CPR = BM / 8;     // 8-channel groups per pixel row
     constexpr int RPP = 256 / CPR;  // pixel rows per pass
-    constexpr int LDSB = TAPR ? 2 * (3 * BM * 128 + (TAPR == 2 ? BN + 8 : BN) * 128)
-                              : 3 * (BM + BN) * 128;  // launched
+    constexpr int LDSB = TAPR ? tapr_lds(BM, BN, TAPR) : ring_lds(BM, BN, 3);  // launched
     static_assert(256 % CPR == 0 && BN * TS * 4 <= LDSB, "staged tile fits the mainloop LDS");
     float* Ts = reinterpret_cast<float*>(smem);
     __syncthreads();  // every wave is done with the mainloop's LDS
@@ -626,9 +544,10 @@ __global__ __launch_bounds__(256) void conv2_kernel(Conv2Args a) {
     // BN-backward operands o / y) is issued before the first is used, so a workgroup pays one
     // memory round trip per chunk instead of one per row (a 1x1 layer with one or two k-steps is
     // all epilogue: ResNet-50's 64 -> 256 forward / 256 -> 64 data gradient at 56x56 ran 3-5x
-    // slower than their HBM bytes with the row loop serialised on its loads).
+    // slower than their HBM bytes with the row loop serialised on its loads;
+    // profiles/r5_epilogue_ab.jsonl).
     constexpr int NIT = BN / RPP;
-    constexpr int UMAX = MODE == 3 ? (PSX_EPI_U < 2 ? PSX_EPI_U : 2) : PSX_EPI_U;  // MODE 3: 4 spills
+    constexpr int UMAX = MODE == 3 ? 2 : 4;  // MODE 3: chunks of 4 spill
     constexpr int U = NIT < UMAX ? NIT : UMAX;
     static_assert(NIT % U == 0, "whole chunks");
     const int pr0 = tid / CPR;
@@ -903,9 +822,16 @@ Plan plan_for(int OC, int npix, int ksteps, bool f32 = false) {
   return p;
 }
 
+// plan -> the launch's tile grid over a.OC channels x npix pixels and its k-steps per split
+void apply_plan(Conv2Args& a, const Plan& p, int npix, int ksteps) {
+  a.n_oc_tiles = a.OC / p.BM;
+  a.n_pix_tiles = (npix + p.BN - 1) / p.BN;
+  a.splits = p.splits;
+  a.kps = (ksteps + p.splits - 1) / p.splits;
+}
+
 // deterministic mode: this launch's slab rows (one per pixel tile, per parity class for MODE 3)
-void with_det(Conv2Args& b, int rows) {
-  (void)rows;
+void with_det(Conv2Args& b) {
   if (b.stats || b.bpart) b.det = det_for(b.bpart ? b.bpart : b.stats);
 }
 
@@ -918,13 +844,13 @@ int launch2(const Conv2Args& a, hipStream_t st) {
   // the ResNet-50 step, r5_call13, kept as the tighter bound)
   const int nk_max = SPLIT ? a.kps : (MODE == 3 ? 3 : a.Kg / kKS<T>);
   const int stages = nk_max < 3 ? (nk_max < 1 ? 1 : nk_max) : (a.nstg == 2 ? 2 : 3);
-  const size_t ring = (size_t)stages * (BM + BN) * 128, epi = (size_t)BN * (BM + 4) * 4;
+  const size_t ring = ring_lds(BM, BN, stages), epi = (size_t)BN * (BM + 4) * 4;
   const size_t red = (size_t)(256 / (BM / 8)) * 3 * BM * 4;  // the epilogue's statistic reduction
   const size_t epr = epi > red ? epi : red;
   const size_t lds = SPLIT ? ring : (ring > epr ? ring : epr);
   dim3 grid(a.n_oc_tiles * a.n_pix_tiles, SPLIT ? a.splits : (MODE == 3 ? 4 : 1));
   Conv2Args b = a;
-  if (!SPLIT) with_det(b, a.n_pix_tiles * (MODE == 3 ? 4 : 1));
+  if (!SPLIT) with_det(b);
   hipLaunchKernelGGL((conv2_kernel<T, BM, BN, MODE, RES, SPLIT, WGM>), grid, dim3(256), lds, st, b);
   return (int)hipGetLastError();
 }
@@ -947,9 +873,9 @@ int dispatch2(const Plan& p, const Conv2Args& a, hipStream_t st) {
 
 template <typename T, int BM, int BN, int MODE, bool RES, int WGM, int TP = 1>
 int launch_tapr(const Conv2Args& a, hipStream_t st) {
-  const size_t lds = (size_t)2 * (3 * BM * 128 + (TP == 2 ? BN + 8 : BN) * 128);
+  const size_t lds = tapr_lds(BM, BN, TP);
   Conv2Args b = a;
-  with_det(b, a.n_pix_tiles);
+  with_det(b);
   hipLaunchKernelGGL((conv2_kernel<T, BM, BN, MODE, RES, false, WGM, TP>), dim3(a.n_oc_tiles * a.n_pix_tiles),
                      dim3(256), lds, st, b);
   return (int)hipGetLastError();
@@ -972,7 +898,7 @@ int tapr_bn(int R, int S, int stride, int pad, int H, int W, int IC, int OC, int
   // per CU) win or tie on every layer — 32x32x64: 27.3/20.9 vs generic 26.3/23.0; 16x16x128:
   // 18.7/15.8 vs 20.6/19.3; 8x8x256: 14.8/13.7 vs 25.5/23.4; 4x4x512: 20.5/19.2 vs 29.3/28.0
   // (generic = split-K + epilogue launch there); 128/256-pixel tiles (1 workgroup per CU) lose.
-  // fp32 (scripts/dev/f32_tapr_sweep.sh, us fwd/dgrad): 256-pixel tiles with 64x64 wave tiles (WGM 1)
+  // fp32 (profiles/r2s3_fp32_layers_ab.jsonl, us fwd/dgrad): 256-pixel tiles with 64x64 wave tiles (WGM 1)
   // win while the grid still has >= 256 workgroups — 32x32x64: 95/94 vs 103/97, 16x16x128: 85/84
   // vs 94/92 — and lose below (8x8x256: 148 vs 89); the f32 MFMA work per stage then hides the
   // DMA wait at one workgroup per CU
@@ -984,12 +910,10 @@ int tapr_bn(int R, int S, int stride, int pad, int H, int W, int IC, int OC, int
   // 32x32x64 24.3 / 31.8 (256-pixel tiles, the round-5 choice) -> 21.5 / 26.9, 16x16x128 18.3 / 20.1 ->
   // 17.2 / 20.6; the bf16 step 1.660 -> 1.605 ms (3 interleaved pairs, profiles/r6_numbers.jsonl)
   if (!force && !f32 && npix % 128 == 0 && 128 % W == 0 && (long)(npix / 128) * (OC / 64) >= 512) BN = 128;
-#if PSX_TAPR_F32_128
   // fp32 with the register double buffer: 128-pixel tiles (two workgroups per CU, one's epilogue
   // under the other's mainloop) where they fill two full rounds of the chip. Same-box A/B: 32x32x64
   // 102.9/96.8 -> 99.2/94.0 us fwd/dgrad, 16x16 equal; bench 4.977 -> 4.936/4.946 ms/step
   if (!force && f32 && npix % 128 == 0 && 128 % W == 0 && (long)(npix / 128) * (OC / 64) >= 512) BN = 128;
-#endif
   if ((BN != 64 && BN != 128 && BN != 256) || BN % W || npix % BN) return 0;
   return BN;
 }
@@ -1060,10 +984,7 @@ int conv_fwd2_t(Conv2Args& a, float* ws, hipStream_t st) {
   if (const int tbn = tapr_bn(a.R, a.S, a.stride, a.pad, a.IH, a.IW, IC, OC, a.npix, sizeof(T) == 4))
     return dispatch_tapr<T, 0, false>(tbn, a, st);
   const Plan p = plan_for(OC, a.npix, Kg / KS, sizeof(T) == 4);
-  a.n_oc_tiles = OC / p.BM;
-  a.n_pix_tiles = (a.npix + p.BN - 1) / p.BN;
-  a.splits = p.splits;
-  a.kps = (Kg / KS + p.splits - 1) / p.splits;
+  apply_plan(a, p, a.npix, Kg / KS);
   if (p.splits > 1 && !ws) return -9;
   int e = dispatch2<T, 0, false>(p, a, st);
   if (e || p.splits == 1) return e;
@@ -1080,10 +1001,7 @@ int conv_dgrad2_t(Conv2Args& a, float* ws, hipStream_t st) {
   if (const int tbn = tapr_bn(a.R, a.S, a.stride, a.pad, H, W, OC_fwd, IC_fwd, a.npix, sizeof(T) == 4))
     return res ? dispatch_tapr<T, 1, true>(tbn, a, st) : dispatch_tapr<T, 1, false>(tbn, a, st);
   const Plan p = plan_for(IC_fwd, a.npix, Kg / KS, sizeof(T) == 4);
-  a.n_oc_tiles = IC_fwd / p.BM;
-  a.n_pix_tiles = (a.npix + p.BN - 1) / p.BN;
-  a.splits = p.splits;
-  a.kps = (Kg / KS + p.splits - 1) / p.splits;
+  apply_plan(a, p, a.npix, Kg / KS);
   const bool parity = a.stride == 2 && a.log2_icc >= 3;
   if (p.splits > 1 && !ws && !parity) return -9;  // the parity-class path never splits K
   int e;
@@ -1096,10 +1014,7 @@ int conv_dgrad2_t(Conv2Args& a, float* ws, hipStream_t st) {
     Plan q = plan_for(IC_fwd, (a.npix + 3) / 4, Kg / KS, sizeof(T) == 4);
     q.splits = 1;
     if (IC_fwd % q.BM) q.BM = 64;
-    a.n_oc_tiles = IC_fwd / q.BM;
-    a.n_pix_tiles = (Nb * ((H + 1) / 2) * ((W + 1) / 2) + q.BN - 1) / q.BN;
-    a.splits = 1;
-    a.kps = Kg / KS;
+    apply_plan(a, q, Nb * ((H + 1) / 2) * ((W + 1) / 2), Kg / KS);
     return res ? dispatch2<T, 3, true>(q, a, st) : dispatch2<T, 3, false>(q, a, st);
   } else if (a.stride == 2)
     e = res ? dispatch2<T, 2, true>(p, a, st) : dispatch2<T, 2, false>(p, a, st);
@@ -1216,12 +1131,6 @@ int psx_conv_dgrad2_sc(const void* dy, const void* wd, void* dx, const void* res
 // 1x4 waves, 3: 64x128 / 1x4 waves; N rows x M pixels).
 // s2 > 1: each batch's Kd-long reduction as s2 ranges (whole k-steps) writing s2 partial slabs
 // P[b s2 + j][M][N] (the Winograd output transform sums them, wino.hip psx_wino_conv)
-// LDS ring depth of the batched GEMMs (Conv2Args::nstg): 2 (5 fp32 64x64 workgroups per CU
-// instead of 3). Same box, wino_conv forward us 3-deep / 2-deep (bench/wino_gemm_ab.py,
-// profiles/r6_wino_gemm_stages_ab.jsonl): 8x8x256 51.0 / 49.9, 4x4x512 45.9 / 44.8, 14x14x256
-// 144.8 / 139.8, 7x7x512 120.9 / 120.1
-static int bgemm_stages() { return 2; }
-
 int psx_bgemm_f32_split(const float* A, const float* B, float* P, const void* zero, int M, int N, int Kd, int nb,
                         int s2, int cfg, hipStream_t st) {
   if (N % 64 || Kd < kKS<float> || (Kd & (Kd - 1)) || M < 1 || nb < 1 || s2 < 1 || (Kd / kKS<float>) % s2) return -2;
@@ -1246,7 +1155,10 @@ int psx_bgemm_f32_split(const float* A, const float* B, float* P, const void* ze
   a.n_pix_tiles = (M + p.BN - 1) / p.BN;
   a.splits = nb * s2;
   a.kps = Kd / kKS<float> / s2;
-  a.nstg = bgemm_stages();
+  // a 2-deep LDS ring (5 fp32 64x64 workgroups per CU instead of 3). Same box, wino_conv forward
+  // us 3-deep / 2-deep (bench/wino_gemm_ab.py, profiles/r6_wino_gemm_stages_ab.jsonl): 8x8x256
+  // 51.0 / 49.9, 4x4x512 45.9 / 44.8, 14x14x256 144.8 / 139.8, 7x7x512 120.9 / 120.1
+  a.nstg = 2;
   return nb * s2 > 1 ? dispatch2<float, 0, false>(p, a, st) : -2;
 }
 

@@ -256,7 +256,7 @@ __global__ __launch_bounds__(1024) void tk_pass_a(const GT* __restrict__ g, floa
 
 
 // B: sure entries -> payload (index order), candidates -> (cidx, cval) (index order) + their
-// coarse / fine histograms. Tiles of 4096 elements, 4 consecutive ones per thread (one 16-byte
+// coarse / fine histograms. Tiles of 1024 elements, 4 consecutive ones per thread (one 16-byte
 // load, three tiles in flight ahead); an element's rank = the preceding waves' counts (one
 // cross-wave prefix per tile, double-buffered so one barrier suffices) + the wave's ballots below
 // it + its own earlier flags.

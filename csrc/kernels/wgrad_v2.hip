@@ -3,13 +3,14 @@
 //
 // Both operands are pixel-major in HBM, so the LDS tiles are pixel-major and the MFMA
 // (v_mfma_f32_16x16x32_bf16) fragments along the pixel (reduction) axis are fetched with the
-// gfx950 transposing LDS read ds_read_b64_tr_b16. Compared with v1 (conv_gemm.hip):
-//   * tiles up to 128 (k) x 128 (oc) — half the LDS fragment traffic per MFMA,
+// gfx950 transposing LDS read ds_read_b64_tr_b16: im2col columns k are the MFMA's M rows, output
+// channels its N columns, so a lane of a 16x16 tile holds 4 consecutive k of one oc.
+//   * tiles up to 128 (k) x 128 (oc),
 //   * global->LDS by global_load_lds with a per-lane im2col source address (padding = zero
 //     page) and the transposed-read swizzle folded into the source address,
 //   * pixel -> (n, oh, ow) and tap -> (r, s) by multiply-high division (no integer divide in
 //     the main loop), 3 LDS stages with counted vmcnt waits and one barrier per 64 pixels.
-// Partial sums go to fp32 slabs [split][OC][Kg] reduced by wgrad_reduce (conv_gemm.hip),
+// Partial sums go to fp32 slabs [split][OC][Kg] reduced by wgrad_reduce (wgrad_reduce.hip),
 // which also permutes to OIHW and emits the fp16 wire codec.
 #include <stdlib.h>
 
@@ -27,8 +28,9 @@ struct Wgrad2Args {
   int n_k_tiles, n_oc_tiles, splits, steps_per_split;  // steps of 64 pixels
 };
 
-// pixel-major tile swizzle for the transposed reads (see conv_gemm.hip pmaj_off for the 128 B
-// case; 256 B rows put each row on its own bank row, so 8 rows x 2 chunks need (r&7)<<1).
+// pixel-major tile swizzle for the transposed reads: 128 B rows share a bank row in pairs, so the
+// chunk index takes two bits of the row pair; 256 B rows put each row on its own bank row, so 8
+// rows x 2 chunks need (r&7)<<1.
 template <int ROWB>
 PSX_DEV int pm2(int r, int c) {
   if constexpr (ROWB == 128) return r * 128 + ((c ^ (((r >> 1) & 3) << 1)) << 4);

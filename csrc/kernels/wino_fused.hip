@@ -52,26 +52,6 @@
 #include "common.hpp"
 #include "wino.hpp"
 
-// diagnostics (A/B builds only, wrong results): bit 1 no B loads, 2 no patch loads, 4 no transform
-// VALU, 8 no V stores, 16 no A reads from LDS, 32 no transform at all (VALU + LDS writes)
-#ifndef PSX_WF_PROBE
-#define PSX_WF_PROBE 0
-#endif
-// bit 1: B operands loaded two k-steps ahead (else one); bit 2: the next k-step's A operands read
-// before this k-step's MFMAs (inside a group)
-#ifndef PSX_WF_PF
-#define PSX_WF_PF 0
-#endif
-#ifndef PSX_WF_SWZ
-#define PSX_WF_SWZ 1
-#endif
-// 1: the first output tile's epilogue operands (res, y1, o, y2) are loaded before the last group's
-// MFMAs; 0: every epilogue load after the group loop; 2 (A/B builds): both tiles' operands early
-// (the residual + mask-from-o + two-BN variants, 2 x 64 values, then spill 22-23 VGPRs)
-#ifndef PSX_WF_EARLY
-#define PSX_WF_EARLY 1
-#endif
-
 namespace psx {
 
 PSX_DEV void mfma_f32_16x16x4(f32x4& acc, float a, float b) {
@@ -209,7 +189,7 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
   // block so the transform's ds_write_b128 (16 lanes of one tile = 16 channels scatter over the 4
   // k-steps and 4 lane groups) hit 16 different bank groups instead of one; the MFMA reads stay a
   // permutation of one contiguous 1 KB block (conflict-free)
-  auto swz = [](int q, int u) { return PSX_WF_SWZ ? (u ^ ((((u >> 4) << 2) + q) & 15)) : u; };
+  auto swz = [](int q, int u) { return u ^ ((((u >> 4) << 2) + q) & 15); };
   float d[36], yb[36];
   auto load_patch = [&](int g) {
     const int so = g * 16 * 4;
@@ -217,8 +197,7 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
     for (int r = 0; r < 6; ++r)
 #pragma unroll
       for (int s = 0; s < 6; ++s)
-        d[r * 6 + s] = (PSX_WF_PROBE & 2) ? (float)(rowoff[r] + coloff[s] + so)
-                                          : __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xr, rowoff[r] + coloff[s], so, 0));
+        d[r * 6 + s] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xr, rowoff[r] + coloff[s], so, 0));
     if (bwdin) {
 #pragma unroll
       for (int r = 0; r < 6; ++r)
@@ -228,7 +207,6 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
     }
   };
   auto xform = [&](int g, int p) {
-    if constexpr ((PSX_WF_PROBE & 32) != 0) return;
     const int ch0 = g * 16;  // wave-uniform
     float sc = 1.f, sh = 0.f;
     if constexpr (IN != kWfPlain) {
@@ -290,7 +268,7 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
       }
       vb[p][qa][5 * hh + 4][swz(qa, la)] = (f32x4){e[18 * hh + 16], e[18 * hh + 17], 0.f, 0.f};
     }
-    if constexpr (HASV && (PSX_WF_PROBE & 8) == 0) {  // the stores cost ~4 us on 32x32x64 even when dropped
+    if constexpr (HASV) {  // the stores cost ~4 us on 32x32x64 even when dropped
 #pragma unroll
       for (int b = 0; b < 36; ++b)
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e[b]), vr, voff, (b * a.T * C + ch0) * 4, 0);
@@ -301,24 +279,22 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
   f32x4 acc[18];
 #pragma unroll
   for (int m = 0; m < 18; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  constexpr int UD = (PSX_WF_PF & 1) ? 2 : 1;  // B prefetch distance (k-steps)
-  f32x4 ub[UD][4];
-  float2 uh[UD];
-  auto load_u = [&](int s, int slot) {
+  // B operands of the next k-step: loaded one k-step ahead (two ahead, and the next k-step's A
+  // operands read before this one's MFMAs, measured no gain: profiles/r3_wino_fused_ab.jsonl)
+  f32x4 ub[4];
+  float2 uh;
+  auto load_u = [&](int s) {
     const int so = ubase + s * 10 * 1024;
-    if constexpr ((PSX_WF_PROBE & 1) != 0) {  // diagnostic: B from registers
-#pragma unroll
-      for (int i = 0; i < 4; ++i) ub[slot][i] = (f32x4){(float)so, 1.f, 2.f, (float)i};
-      uh[slot] = make_float2((float)so, 1.f);
-      return;
-    }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      ub[slot][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ur, l * 16 + i * 1024, so, 0));
-    uh[slot] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(ur, l * 16 + 4 * 1024, so, 0));
+      ub[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ur, l * 16 + i * 1024, so, 0));
+    uh = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(ur, l * 16 + 4 * 1024, so, 0));
   };
+  // k-step 0, as a one-trip loop: hipcc derives the clamp of a loop counter, here and in the group
+  // loop, in one form and shares it; from a literal 0 it picks another and the scalar code of every
+  // instantiation changes (same work, other instructions)
 #pragma unroll
-  for (int i = 0; i < UD; ++i) load_u(i < S4 ? i : S4 - 1, i);
+  for (int s = 0; s < 1; ++s) load_u(s < S4 ? s : S4 - 1);
   if (h == 0) {
     load_patch(0);
     xform(0, 0);
@@ -333,25 +309,17 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
   f32x4 an[4];
   float2 ah;
   auto load_a = [&](int p, int q) {
-    if constexpr ((PSX_WF_PROBE & 16) != 0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) an[i] = (f32x4){(float)p, (float)q, (float)i, 1.f};
-      ah = make_float2((float)q, 2.f);
-      return;
-    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) an[i] = vb[p][q][5 * h + i][swz(q, l)];
     ah = *reinterpret_cast<const float2*>(&vb[p][q][5 * h + 4][swz(q, l)]);
   };
   // Epilogue operands (res, y1, o, y2) of the lane's output pixels: tile ii of its two, 16 pixels,
-  // channel k. The first tile's are issued before the last group's MFMAs (PSX_WF_EARLY; the patch
-  // registers are free by then), the second tile's in the epilogue.
+  // channel k. The first tile's are issued before the last group's MFMAs (the patch registers are
+  // free by then), the second tile's in the epilogue: both tiles early spills 22-23 VGPRs in the
+  // residual + mask-from-o + two-BN variants (2 x 64 values; profiles/r7_wino_fused_early_ab.jsonl).
   const int k = kb * kWfK + kq * 16 + (l & 15);
   constexpr bool bwd = BWD, two = BWD && TWO;
   const int ybytes = a.ybytes;
-#ifdef PSX_WF_RES_BUF
-  const auto rr_ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res), 0, RES ? ybytes : 0, 0x00020000);
-#endif
   const auto y1r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bs.y1), 0, bwd ? ybytes : 0, 0x00020000);
   const auto orr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bs.o), 0, (bwd && !MAFF) ? ybytes : 0,
                                                      0x00020000);
@@ -369,12 +337,8 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
       const int so = ((e >> 2) * W + (e & 3)) * K * 4;
       // the residual through a flat load: its buffer descriptor's 4 SGPRs pushed the residual +
       // data-gradient variants into SGPR spills held in VGPR lanes and then 25-144 VGPR spills to
-      // scratch (113 vs 66 us per 32x32x64 call, profiles/README.md round-5 leads)
-#ifdef PSX_WF_RES_BUF  // A/B builds: the buffer load
-      if constexpr (RES) rv[ii][e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr_, base, so, 0));
-#else
+      // scratch (113 vs 66 us per 32x32x64 call, profiles/r5_wino_fused_res_spill_ab.jsonl)
       if constexpr (RES) rv[ii][e] = a.res[(base + so) >> 2];
-#endif
       if constexpr (bwd) {
         y1v[ii][e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(y1r, base, so, 0));
         if constexpr (!MAFF) ov[ii][e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(orr, base, so, 0));
@@ -382,32 +346,25 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
       }
     }
   };
-  constexpr bool early = PSX_WF_EARLY && (RES || BWD);
+  constexpr bool early = RES || BWD;
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     const int p = g & 1;
     if constexpr (early)
-      if (g == G - 1) {
-        load_epi(0);
-        if constexpr (PSX_WF_EARLY > 1) load_epi(1);
-      }
+      if (g == G - 1) load_epi(0);
     if (h == 0) {
       if (g + 1 < G) xform(g + 1, p ^ 1);
       if (g + 2 < G) load_patch(g + 2);
     }
-    if constexpr ((PSX_WF_PF & 2) != 0) load_a(p, 0);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int s = g * 4 + q;
-      if constexpr ((PSX_WF_PF & 2) == 0) load_a(p, q);
+      load_a(p, q);
       const f32x4 a0 = an[0], a1 = an[1], a2 = an[2], a3 = an[3];
       const float2 a4 = ah;
-      if constexpr ((PSX_WF_PF & 2) != 0)
-        if (q < 3) load_a(p, q + 1);
-      const int us = s % UD;
-      const f32x4 u0 = ub[us][0], u1 = ub[us][1], u2 = ub[us][2], u3 = ub[us][3];
-      const float2 u4 = uh[us];
-      load_u(s + UD < S4 ? s + UD : S4 - 1, us);  // UD k-steps ahead (past the end: re-loads the last)
+      const f32x4 u0 = ub[0], u1 = ub[1], u2 = ub[2], u3 = ub[3];
+      const float2 u4 = uh;
+      load_u(s + 1 < S4 ? s + 1 : S4 - 1);  // one k-step ahead (past the end: re-loads the last)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         mfma_f32_16x16x4(acc[j], a0[j], u0[j]);
@@ -507,7 +464,7 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(WinoFusedArgs a, Win
 #pragma unroll
   for (int ii = 0; ii < 2; ++ii) {
     const int base = out_base(ii);
-    if (!(early && (ii == 0 || PSX_WF_EARLY > 1))) load_epi(ii);
+    if (!(early && ii == 0)) load_epi(ii);
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int so = ((e >> 2) * W + (e & 3)) * K * 4;

@@ -48,16 +48,6 @@ struct WinoWgradArgs {
   int xbytes, ybytes;         // N H W C * 4, N H W K * 4 (< 2^30)
 };
 
-// PSX_WGF_PF = 1: the next tile group's 52 (BWD: 68) loads are issued before the current group's
-// transforms and MFMAs (one wave per SIMD: the accumulators move to AGPRs); 0 (default): load,
-// then compute, two waves per SIMD hiding each other's load latency. Same box, B = 128, us incl.
-// the output transform (bench/wino_wgrad_ab.py): 32x32x64 82.8 vs 58.4, 16x16x128 72.1 vs 55.3,
-// 8x8x256 73.2 vs 53.7, 4x4x512 85.8 vs 61.7 — one wave per SIMD cannot overlap its own
-// transforms with its MFMAs.
-#ifndef PSX_WGF_PF
-#define PSX_WGF_PF 0
-#endif
-
 // one axis of B^T d with explicit FMAs (the file is built without FP contraction, so every
 // template instance rounds identically: the folded and unfolded paths give the same bits)
 PSX_DEV void bt6f(const float (&d)[6], float (&r)[6]) {
@@ -88,7 +78,7 @@ struct WgfRaw {  // one tile group's loads, per lane (its tile, its channel)
 };
 
 template <bool AFF, bool BWD>
-__global__ __launch_bounds__(256, PSX_WGF_PF ? 1 : 2) void wino_wgrad_fused_kernel(WinoWgradArgs a) {
+__global__ __launch_bounds__(256, 2) void wino_wgrad_fused_kernel(WinoWgradArgs a) {
   __shared__ float red[4][9][256];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int nkb = a.K >> 4, nblk = nkb * (a.C >> 4);
@@ -208,24 +198,17 @@ __global__ __launch_bounds__(256, PSX_WGF_PF ? 1 : 2) void wino_wgrad_fused_kern
     }
   };
 
-#if PSX_WGF_PF
-  WgfRaw<BWD> cur;
-  int g = wv * 4;
-  if (g < a.tpr) load(g, cur);
-  for (; g < a.tpr; g += 16) {
-    WgfRaw<BWD> nxt;
-    const bool more = g + 16 < a.tpr;
-    if (more) load(g + 16, nxt);
-    compute(cur);
-    if (more) cur = nxt;  // register moves (a two-set ping-pong unrolled into spills)
-  }
-#else#else
+  // Load, then compute: two waves per SIMD hide each other's load latency. Issuing the next tile
+  // group's 52 (BWD: 68) loads before the current group's transforms and MFMAs needs one wave per
+  // SIMD (the accumulators move to AGPRs), which cannot overlap its own transforms with its MFMAs.
+  // Same box, B = 128, us incl. the output transform, prefetch vs this loop
+  // (profiles/r4_wino_wgrad_ab_prefetch.jsonl): 32x32x64 82.8 vs 58.4, 16x16x128 72.1 vs 55.3,
+  // 8x8x256 73.2 vs 53.7, 4x4x512 85.8 vs 61.7.
   for (int g = wv * 4; g < a.tpr; g += 16) {
     WgfRaw<BWD> cur;
     load(g, cur);
     compute(cur);
   }
-#endif
 
   // the four waves' partial sums, 9 points at a time, added in wave order; lane l holds
   // M[b][k = 4 (l >> 4) + j][c = l & 15] in acc[b][j]

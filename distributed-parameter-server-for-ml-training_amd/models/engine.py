@@ -430,8 +430,8 @@ class HipResNetEngine:
             return
         fuse = True  # the fused single-launch kernel (wino_fused.hip) wherever it applies
         # fused weight gradient (wino_wgrad.hip) on images of at least 16x16: same box,
-        # B = 128, us incl. output transform, fused vs three-launch (bench/wino_wgrad_ab.py,
-        # profiles/r4_wino_wgrad_ab.jsonl): 32x32x64 58.4 vs 71.2, 16x16x128 55.3 vs 46.9 (+ the
+        # B = 128, us incl. output transform, fused vs three-launch (profiles/r4_wino_wgrad_ab.jsonl,
+        # one row per layer): 32x32x64 58.4 vs 71.2, 16x16x128 55.3 vs 46.9 (+ the
         # forward's V store the three-launch path needs, ~7), 8x8x256 53.7 vs 43.2, 4x4x512 61.7 vs
         # 44.1. In the step (side stream; the forward's V store is on the critical path) same box:
         # off 3.568, >= 32 3.412, >= 16 3.363-3.372 ms/step (profiles/r4_numbers.jsonl)
@@ -1020,7 +1020,7 @@ class HipResNetEngine:
                 ds, dbn = b.down
                 self._wgrad(ds, d["inp"], d["dys"])
                 # the 1x1 / stride-2 shortcut's data gradient folded into the 3x3 / stride-2 one
-                # (PSX_TUNE dgrad_fold_sc=0: two launches + a residual pass)
+                # (a layer the kernel cannot fold: two launches + a residual pass)
                 if not (self.fold_sc and self._dgrad(cs, dys[0], d["gin"], bn_next=self._bn_into(j),
                                                      sc=(ds, d["dys"]))):
                     self._dgrad(ds, d["dys"], d["dxs"])
