@@ -822,12 +822,30 @@ Plan plan_for(int OC, int npix, int ksteps, bool f32 = false) {
   return p;
 }
 
-// plan -> the launch's tile grid over a.OC channels x npix pixels and its k-steps per split
-void apply_plan(Conv2Args& a, const Plan& p, int npix, int ksteps) {
-  a.n_oc_tiles = a.OC / p.BM;
-  a.n_pix_tiles = (npix + p.BN - 1) / p.BN;
-  a.splits = p.splits;
-  a.kps = (ksteps + p.splits - 1) / p.splits;
+// The launch decision of one conv: which mainloop (kind, MODE), which tiles, how many splits. Made
+// once per call by route_fwd / route_dgrad below, from the launch's geometry alone; the
+// dispatchers launch what it says and psx_conv2_path reports it, so the two cannot drift.
+struct Route {
+  int err = 0;    // < 0: refused on the host (-2 shape, -4 stride, -11 the shortcut cannot fold)
+  int kind = 0;   // 0 generic mainloop, 1 tap reuse over whole image rows, 2 tap reuse with halo
+  int mode = 0;   // conv2_kernel MODE
+  Plan p{64, 64, 1};
+  int pix_tiles = 0, kps = 0;
+  int pre_splits = 1;  // dgrad: the splits of the unsplit-class plan (the -9 check comes before -11 / -4)
+};
+
+// plan -> the tile grid over npix pixels and the k-steps per split
+void route_plan(Route& r, const Plan& p, int npix, int ksteps) {
+  r.p = p;
+  r.pix_tiles = (npix + p.BN - 1) / p.BN;
+  r.kps = (ksteps + p.splits - 1) / p.splits;
+}
+
+void apply_route(Conv2Args& a, const Route& r) {
+  a.n_oc_tiles = a.OC / r.p.BM;
+  a.n_pix_tiles = r.pix_tiles;
+  a.splits = r.p.splits;
+  a.kps = r.kps;
 }
 
 // deterministic mode: this launch's slab rows (one per pixel tile, per parity class for MODE 3)
@@ -922,18 +940,73 @@ int tapr_bn(int R, int S, int stride, int pad, int H, int W, int IC, int OC, int
 // at every tile width x 2-8 splits on ResNet-18's four 3x3 layers, bench/conv_layers.py: slower on
 // every one — the 4x4x512 layer's best 23.6 vs 21.2 us unsplit — profiles/r6_tapr_split_sweep.txt.)
 template <typename T, int MODE, bool RES>
-int dispatch_tapr(int bn, Conv2Args& a, hipStream_t st) {
-  a.n_oc_tiles = a.OC / 64;
-  a.splits = 1;
-  a.kps = a.Kg / kKS<T>;
-  if (bn < 0) {  // halo mode
-    a.n_pix_tiles = (a.npix + 63) / 64;
-    return launch_tapr<T, 64, 64, MODE, RES, 2, 2>(a, st);
-  }
-  a.n_pix_tiles = a.npix / bn;
-  if (bn == 256) return launch_tapr<T, 64, 256, MODE, RES, 1>(a, st);
-  if (bn == 128) return launch_tapr<T, 64, 128, MODE, RES, 2>(a, st);
+int dispatch_tapr(const Route& r, const Conv2Args& a, hipStream_t st) {
+  if (r.kind == 2) return launch_tapr<T, 64, 64, MODE, RES, 2, 2>(a, st);  // halo mode
+  if (r.p.BN == 256) return launch_tapr<T, 64, 256, MODE, RES, 1>(a, st);
+  if (r.p.BN == 128) return launch_tapr<T, 64, 128, MODE, RES, 2>(a, st);
   return launch_tapr<T, 64, 64, MODE, RES, 2>(a, st);
+}
+
+// tap reuse (tbn = tapr_bn's answer, nonzero): 64-channel tiles, no split-K; halo mode (tbn < 0)
+// 64-pixel tiles with a partial last one, else whole tiles of tbn pixels (1x4 waves at 256)
+void route_tapr(Route& r, int tbn, int npix, int ksteps) {
+  r.kind = tbn < 0 ? 2 : 1;
+  r.p = Plan{64, tbn < 0 ? 64 : tbn, 1, tbn == 256 ? 1 : 2};
+  r.pix_tiles = tbn < 0 ? (npix + 63) / 64 : npix / tbn;
+  r.kps = ksteps;
+}
+
+// a: the geometry fields of psx_conv_fwd2 (fill_fwd)
+Route route_fwd(const Conv2Args& a, bool f32) {
+  Route r;
+  const int KS = f32 ? kKS<float> : kKS<uint16_t>, EPC = f32 ? kEPC<float> : kEPC<uint16_t>;
+  if (a.OC % 64 || a.Kg % KS || a.IC % EPC || (a.IC & (a.IC - 1))) {
+    r.err = -2;
+    return r;
+  }
+  if (const int tbn = tapr_bn(a.R, a.S, a.stride, a.pad, a.IH, a.IW, a.IC, a.OC, a.npix, f32)) {
+    route_tapr(r, tbn, a.npix, a.Kg / KS);
+    return r;
+  }
+  route_plan(r, plan_for(a.OC, a.npix, a.Kg / KS, f32), a.npix, a.Kg / KS);
+  return r;
+}
+
+// a: the geometry fields of psx_conv_dgrad2_sc (fill_dgrad): a.IC = OC_fwd, a.OC = IC_fwd, out =
+// dx; fold: the shortcut fold is asked for (psx_conv_dgrad2_sc with dy_sc)
+Route route_dgrad(const Conv2Args& a, bool f32, bool fold) {
+  Route r;
+  const int KS = f32 ? kKS<float> : kKS<uint16_t>, EPC = f32 ? kEPC<float> : kEPC<uint16_t>;
+  const int OC_fwd = a.IC, IC_fwd = a.OC, H = a.OH, W = a.OW;
+  if (IC_fwd % 64 || a.Kg % KS || (OC_fwd & (OC_fwd - 1)) || OC_fwd % EPC) {
+    r.err = -2;
+    return r;
+  }
+  r.mode = 1;
+  if (const int tbn = tapr_bn(a.R, a.S, a.stride, a.pad, H, W, OC_fwd, IC_fwd, a.npix, f32)) {
+    route_tapr(r, tbn, a.npix, a.Kg / KS);
+    return r;
+  }
+  const Plan p = plan_for(IC_fwd, a.npix, a.Kg / KS, f32);
+  route_plan(r, p, a.npix, a.Kg / KS);
+  r.pre_splits = p.splits;
+  const bool parity = a.stride == 2 && ilog2i(OC_fwd / EPC) >= 3;
+  if (a.stride == 1) return r;
+  if (fold && !parity) {
+    r.err = -11;  // the shortcut folds only into the parity-class path
+  } else if (parity) {
+    // parity classes: each class GEMM covers dx pixels (2i+py, 2j+px), ~1/4 of them
+    Plan q = plan_for(IC_fwd, (a.npix + 3) / 4, a.Kg / KS, f32);
+    q.splits = 1;
+    if (IC_fwd % q.BM) q.BM = 64;
+    route_plan(r, q, a.Nb * ((H + 1) / 2) * ((W + 1) / 2), a.Kg / KS);
+    r.mode = 3;
+  } else if (a.stride == 2) {
+    r.mode = 2;
+  } else {
+    r.err = -4;
+  }
+  return r;
 }
 
 template <typename T>
@@ -977,56 +1050,97 @@ namespace {
 
 template <typename T>
 int conv_fwd2_t(Conv2Args& a, float* ws, hipStream_t st) {
-  constexpr int KS = kKS<T>;
-  const int IC = a.IC, OC = a.OC, Kg = a.Kg;
-  a.log2_icc = ilog2i(IC / kEPC<T>);
-  if (OC % 64 || Kg % KS || IC % kEPC<T> || (IC & (IC - 1))) return -2;
-  if (const int tbn = tapr_bn(a.R, a.S, a.stride, a.pad, a.IH, a.IW, IC, OC, a.npix, sizeof(T) == 4))
-    return dispatch_tapr<T, 0, false>(tbn, a, st);
-  const Plan p = plan_for(OC, a.npix, Kg / KS, sizeof(T) == 4);
-  apply_plan(a, p, a.npix, Kg / KS);
-  if (p.splits > 1 && !ws) return -9;
-  int e = dispatch2<T, 0, false>(p, a, st);
-  if (e || p.splits == 1) return e;
+  a.log2_icc = ilog2i(a.IC / kEPC<T>);
+  const Route r = route_fwd(a, sizeof(T) == 4);
+  if (r.err) return r.err;
+  apply_route(a, r);
+  if (r.kind) return dispatch_tapr<T, 0, false>(r, a, st);
+  if (r.p.splits > 1 && !ws) return -9;
+  int e = dispatch2<T, 0, false>(r.p, a, st);
+  if (e || r.p.splits == 1) return e;
   return finish_split<T>(a, st);
 }
 
 template <typename T>
 int conv_dgrad2_t(Conv2Args& a, float* ws, hipStream_t st) {
-  constexpr int KS = kKS<T>;
-  const int OC_fwd = a.IC, IC_fwd = a.OC, Kg = a.Kg, Nb = a.Nb, H = a.OH, W = a.OW;
-  a.log2_icc = ilog2i(OC_fwd / kEPC<T>);
-  if (IC_fwd % 64 || Kg % KS || (OC_fwd & (OC_fwd - 1)) || OC_fwd % kEPC<T>) return -2;
+  a.log2_icc = ilog2i(a.IC / kEPC<T>);
+  const Route r = route_dgrad(a, sizeof(T) == 4, a.in2 != nullptr);
+  if (r.err == -2) return -2;
   const bool res = a.res != nullptr;
-  if (const int tbn = tapr_bn(a.R, a.S, a.stride, a.pad, H, W, OC_fwd, IC_fwd, a.npix, sizeof(T) == 4))
-    return res ? dispatch_tapr<T, 1, true>(tbn, a, st) : dispatch_tapr<T, 1, false>(tbn, a, st);
-  const Plan p = plan_for(IC_fwd, a.npix, Kg / KS, sizeof(T) == 4);
-  apply_plan(a, p, a.npix, Kg / KS);
-  const bool parity = a.stride == 2 && a.log2_icc >= 3;
-  if (p.splits > 1 && !ws && !parity) return -9;  // the parity-class path never splits K
+  if (r.kind) {
+    apply_route(a, r);
+    return res ? dispatch_tapr<T, 1, true>(r, a, st) : dispatch_tapr<T, 1, false>(r, a, st);
+  }
+  if (r.pre_splits > 1 && !ws && r.mode != 3) return -9;  // the parity-class path never splits K
+  if (r.err) return r.err;
+  apply_route(a, r);
+  const Plan& p = r.p;
   int e;
-  if (a.stride == 1)
+  if (r.mode == 1)
     e = res ? dispatch2<T, 1, true>(p, a, st) : dispatch2<T, 1, false>(p, a, st);
-  else if (a.in2 && !(a.stride == 2 && a.log2_icc >= 3))
-    return -11;  // the shortcut folds only into the parity-class path
-  else if (parity) {
-    // parity classes: each class GEMM covers dx pixels (2i+py, 2j+px), ~1/4 of them
-    Plan q = plan_for(IC_fwd, (a.npix + 3) / 4, Kg / KS, sizeof(T) == 4);
-    q.splits = 1;
-    if (IC_fwd % q.BM) q.BM = 64;
-    apply_plan(a, q, Nb * ((H + 1) / 2) * ((W + 1) / 2), Kg / KS);
-    return res ? dispatch2<T, 3, true>(q, a, st) : dispatch2<T, 3, false>(q, a, st);
-  } else if (a.stride == 2)
-    e = res ? dispatch2<T, 2, true>(p, a, st) : dispatch2<T, 2, false>(p, a, st);
+  else if (r.mode == 3)
+    return res ? dispatch2<T, 3, true>(p, a, st) : dispatch2<T, 3, false>(p, a, st);
   else
-    return -4;
+    e = res ? dispatch2<T, 2, true>(p, a, st) : dispatch2<T, 2, false>(p, a, st);
   if (e || p.splits == 1) return e;
   return finish_split<T>(a, st);
 }
 
+// the geometry fields of a forward launch / a data-gradient launch (H, W: the input image of the
+// forward conv = dx)
+void fill_fwd(Conv2Args& a, int Nb, int H, int W, int IC, int OC, int R, int S, int stride, int pad, int Kg) {
+  a.Nb = Nb; a.IH = H; a.IW = W; a.IC = IC;
+  a.OH = (H + 2 * pad - R) / stride + 1;
+  a.OW = (W + 2 * pad - S) / stride + 1;
+  a.OC = OC; a.R = R; a.S = S; a.pad = pad; a.stride = stride;
+  a.Kg = Kg;
+  a.npix = Nb * a.OH * a.OW;
+}
+
+void fill_dgrad(Conv2Args& a, int Nb, int H, int W, int IC_fwd, int OC_fwd, int R, int S, int stride, int pad,
+                int Kg) {
+  const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
+  a.Nb = Nb; a.IH = P; a.IW = Q; a.IC = OC_fwd;
+  a.OH = H; a.OW = W; a.OC = IC_fwd;
+  a.R = R; a.S = S; a.pad = pad; a.stride = stride;
+  a.Kg = Kg;
+  a.npix = Nb * H * W;
+}
+
+// the layer geometry the shortcut fold needs: a 3x3 / stride-2 / pad-1 conv (its block's shortcut
+// is then the 1x1 / stride-2 / pad-0 one). psx_conv_dgrad2_sc also refuses a residual and a
+// shortcut weight row that is not OC_fwd long: properties of its operands, not of the geometry.
+bool fold_geometry(int R, int S, int stride, int pad) { return R == 3 && S == 3 && stride == 2 && pad == 1; }
+
 }  // namespace
 
 extern "C" {
+
+// Which kernel a conv launch of this geometry takes, without launching anything: the decision of
+// route_fwd / route_dgrad that psx_conv_fwd2 / psx_conv_dgrad2[_sc] act on (PSX_TUNE overrides
+// included: read at every call). dir: 0 forward, 1 data gradient, 2 data gradient with the folded
+// shortcut; the other arguments as those entries take them (dgrad: H, W of dx, IC = IC_fwd, OC =
+// OC_fwd, Kg = Kgd). out[8]: kind (0 generic, 1 tap reuse over whole rows, 2 tap reuse with halo),
+// MODE, BM, BN, WGM, splits, k-steps per split, pixel tiles (per parity class for MODE 3). Returns
+// 0 or the entry's own refusal of the geometry (-2, -4, -11: fold_geometry and the parity path; the
+// fold's operand conditions, a residual or Kg_sc != OC_fwd, and -9, no workspace, are the caller's).
+int psx_conv2_path(int dir, int Nb, int H, int W, int IC, int OC, int R, int S, int stride, int pad, int Kg, int f32,
+                   int* out) {
+  Conv2Args a{};
+  Route r;
+  if (dir == 0) {
+    fill_fwd(a, Nb, H, W, IC, OC, R, S, stride, pad, Kg);
+    r = route_fwd(a, f32 != 0);
+  } else {
+    if (dir == 2 && !fold_geometry(R, S, stride, pad)) return -11;
+    fill_dgrad(a, Nb, H, W, IC, OC, R, S, stride, pad, Kg);
+    r = route_dgrad(a, f32 != 0, dir == 2);
+  }
+  if (r.err) return r.err;
+  const int v[8] = {r.kind, r.mode, r.p.BM, r.p.BN, r.p.WGM, r.p.splits, r.kps, r.pix_tiles};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  return 0;
+}
 
 // Bytes of fp32 split-K workspace the v2 conv needs for this problem (0 = no split).
 // f32: the operands are fp32 (32-channel k-steps) instead of bf16.
@@ -1060,12 +1174,7 @@ int psx_conv_fwd2(const void* x, const void* wf, void* y, float* stats, const vo
   a.stats = stats;
   a.part = ws;
   a.zero = zero;
-  a.Nb = Nb; a.IH = H; a.IW = W; a.IC = IC;
-  a.OH = (H + 2 * pad - R) / stride + 1;
-  a.OW = (W + 2 * pad - S) / stride + 1;
-  a.OC = OC; a.R = R; a.S = S; a.pad = pad; a.stride = stride;
-  a.Kg = Kg;
-  a.npix = Nb * a.OH * a.OW;
+  fill_fwd(a, Nb, H, W, IC, OC, R, S, stride, pad, Kg);
   return f32 ? conv_fwd2_t<float>(a, ws, st) : conv_fwd2_t<uint16_t>(a, ws, st);
 }
 
@@ -1092,7 +1201,7 @@ int psx_conv_dgrad2_sc(const void* dy, const void* wd, void* dx, const void* res
                        hipStream_t st) {
   Conv2Args a{};
   if (dy_sc) {
-    if (R != 3 || S != 3 || stride != 2 || pad != 1 || res || Kg_sc != OC_fwd || !wd_sc) return -11;
+    if (!fold_geometry(R, S, stride, pad) || res || Kg_sc != OC_fwd || !wd_sc) return -11;
     a.in2 = dy_sc;
     a.w2 = wd_sc;
     a.Kg2 = Kg_sc;
@@ -1107,7 +1216,6 @@ int psx_conv_dgrad2_sc(const void* dy, const void* wd, void* dx, const void* res
     a.bns = bst->y2 ? 3 : 2;
     a.bmask = bst->mask_store;
   }
-  const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
   a.in = dy;
   a.w = wd;
   a.out = dx;
@@ -1115,11 +1223,7 @@ int psx_conv_dgrad2_sc(const void* dy, const void* wd, void* dx, const void* res
   a.stats = nullptr;
   a.part = ws;
   a.zero = zero;
-  a.Nb = Nb; a.IH = P; a.IW = Q; a.IC = OC_fwd;
-  a.OH = H; a.OW = W; a.OC = IC_fwd;
-  a.R = R; a.S = S; a.pad = pad; a.stride = stride;
-  a.Kg = Kg;
-  a.npix = Nb * H * W;
+  fill_dgrad(a, Nb, H, W, IC_fwd, OC_fwd, R, S, stride, pad, Kg);
   return f32 ? conv_dgrad2_t<float>(a, ws, st) : conv_dgrad2_t<uint16_t>(a, ws, st);
 }
 

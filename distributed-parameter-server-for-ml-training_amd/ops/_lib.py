@@ -44,6 +44,8 @@ _KERNEL_SIGS = {
     "psx_wgrad_reduce": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, i32, vp]),
     "psx_wgrad_reduce_batch": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp]),
     "psx_conv2_workspace": (i64, [i32, i32, i32, i32, i32, i32]),
+    "psx_conv2_path": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
+    "psx_bgemm_f32_split": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "psx_conv_wgrad2": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "psx_conv_fwd2": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp,
                             vp]),

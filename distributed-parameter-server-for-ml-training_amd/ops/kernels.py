@@ -87,6 +87,27 @@ def conv2_workspace_bytes(nb, oh, ow, oc, kg, f32=False) -> int:
     return int(kernels().psx_conv2_workspace(nb, oh, ow, oc, kg, int(bool(f32))))
 
 
+CONV2_KINDS = ("generic", "tapr_rows", "tapr_halo")
+CONV2_DIRS = {"fwd": 0, "dgrad": 1, "dgrad_sc": 2}
+
+
+def conv2_path(direction, nb, h, w, ic, oc, k, stride, pad, kg, f32=False):
+    """Which kernel conv_fwd2 / conv_dgrad2 / conv_dgrad2_sc would launch for this geometry, on the
+    host alone (csrc/kernels/conv_v2.hip psx_conv2_path: the dispatchers' own decision, PSX_TUNE
+    included). ``direction``: "fwd", "dgrad" or "dgrad_sc"; the other arguments as those entries
+    take them (dgrad: h, w of dx, ic / oc of the forward conv, kg = kgd). Returns a dict: kind
+    (one of CONV2_KINDS), mode (conv2_kernel MODE 0-3), bm, bn, wgm, splits, kps (k-steps per
+    split), pix_tiles (per parity class for mode 3); or the negative code the entry would refuse
+    the geometry with (-2, -4, -11)."""
+    out = (C.c_int * 8)()
+    rc = int(kernels().psx_conv2_path(CONV2_DIRS[direction], nb, h, w, ic, oc, k, k, stride, pad, kg,
+                                      int(bool(f32)), out))
+    if rc:
+        return rc
+    v = list(out)
+    return dict(kind=CONV2_KINDS[v[0]], mode=v[1], bm=v[2], bn=v[3], wgm=v[4], splits=v[5], kps=v[6], pix_tiles=v[7])
+
+
 class BnFin(C.Structure):
     """csrc/kernels/bnfin.hpp BnFin: in-launch forward BN finalize descriptor."""
     _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("run_mean", C.c_void_p), ("run_var", C.c_void_p),
@@ -193,6 +214,16 @@ def bgemm_f32(a, b, p, m, n, kd, nb, cfg=0):
     assert a.numel() >= m * nb * kd and b.numel() >= n * nb * kd and p.numel() >= nb * m * n
     check(kernels().psx_bgemm_f32(ptr(a), ptr(b), ptr(p), ptr(zero_page(a.device)), m, n, kd, nb, cfg, stream_ptr()),
           "bgemm_f32")
+
+
+def bgemm_f32_split(a, b, p, m, n, kd, nb, s2, cfg=0) -> int:
+    """bgemm_f32 with each batch's reduction cut into ``s2`` ranges of whole k-steps: p
+    [nb * s2][m][n] partial slabs (psx_bgemm_f32_split). Returns the entry's code: 0, or -2 for a
+    shape it refuses (n % 64, kd no power of two >= 32, (kd / 32) % s2, one slab in all)."""
+    assert a.dtype == b.dtype == p.dtype == torch.float32
+    assert a.numel() >= m * nb * kd and b.numel() >= n * nb * kd and p.numel() >= nb * s2 * m * n
+    return int(kernels().psx_bgemm_f32_split(ptr(a), ptr(b), ptr(p), ptr(zero_page(a.device)), m, n, kd, nb, s2, cfg,
+                                             stream_ptr()))
 
 
 def bgemm_tn_f32(x, d, part, t, c, k, nb, q=1, br=64, bc=64):
