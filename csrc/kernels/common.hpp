@@ -37,7 +37,7 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 namespace psx {
 
 // Developer tuning overrides — the planners' tile sweeps and A/B switches — in ONE environment
-// variable, PSX_TUNE="key=value[,key=value...]" (e.g. PSX_TUNE=cv_bm=128,wg_splits=12; a bare
+// variable, PSX_TUNE="key=value[,key=value...]" (e.g. PSX_TUNE=cv_bm=128,cv_splits=2; a bare
 // key means "1"; the Python side reads the same variable, psx/utils/tune.py). Read at every
 // planning call (tests and sweeps change it inside one process). Returns the value (a per-thread
 // buffer) or nullptr when the key is absent. Production runs set nothing.

@@ -41,6 +41,19 @@ PSX_DEV s16x4 tr_read2(const unsigned char* base, int off) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off));
 }
 
+// wait until at most `ahead` later stage groups (PER DMA ops each) are still in flight
+template <int PER, int MAXA>
+PSX_DEV void wait_ahead(int ahead) {
+  if constexpr (MAXA <= 0) {
+    wait_vmcnt<0>();
+  } else {
+    if (ahead >= MAXA)
+      wait_vmcnt<MAXA * PER>();
+    else
+      wait_ahead<PER, MAXA - 1>(ahead);
+  }
+}
+
 template <int BR, int BC, int NS>
 __global__ __launch_bounds__(256) void wgrad2_kernel(Wgrad2Args a) {
   constexpr int XROWB = BR * 2, DROWB = BC * 2;           // bytes per pixel row
@@ -138,13 +151,7 @@ __global__ __launch_bounds__(256) void wgrad2_kernel(Wgrad2Args a) {
   // unrolled by NS: compile-time stage offsets (see wgrad3_kernel)
   auto step = [&](const int st, auto sc) {
     constexpr int stage = decltype(sc)::value;
-    const int ahead = min(NS - 2, nsteps - 1 - st);  // groups issued after step st's
-    if (ahead >= NS - 2)
-      wait_vmcnt<(NS - 2) * (LX + LD)>();
-    else if (NS > 3 && ahead == 1)
-      wait_vmcnt<LX + LD>();
-    else
-      wait_vmcnt<0>();
+    wait_ahead<LX + LD, NS - 2>(min(NS - 2, nsteps - 1 - st));  // groups issued after step st's
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (st + NS - 1 < nsteps) issue(st + NS - 1, stage == 0 ? NS - 1 : stage - 1);
@@ -306,13 +313,7 @@ __global__ __launch_bounds__(256) void wgrad2f_kernel(Wgrad2Args a) {
   // unrolled by NS: compile-time stage offsets (see wgrad3_kernel)
   auto step = [&](const int st, auto sc) {
     constexpr int stage = decltype(sc)::value;
-    const int ahead = min(NS - 2, nsteps - 1 - st);
-    if (ahead >= NS - 2)
-      wait_vmcnt<(NS - 2) * (LX + LD)>();
-    else if (NS > 3 && ahead == 1)
-      wait_vmcnt<LX + LD>();
-    else
-      wait_vmcnt<0>();
+    wait_ahead<LX + LD, NS - 2>(min(NS - 2, nsteps - 1 - st));
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (st + NS - 1 < nsteps) issue(st + NS - 1, stage == 0 ? NS - 1 : stage - 1);
@@ -362,28 +363,15 @@ __global__ __launch_bounds__(256) void wgrad2f_kernel(Wgrad2Args a) {
 // rows of any W dividing 56 — in the 64-row tiles; rows 56..63 are zero on both operands (1/8 of
 // the MFMA work idle), pixel -> (oh, ow) by multiply-high division.
 struct Wgrad3Args {
-  const uint16_t* x;
-  const uint16_t* dy;
-  float* part;
-  const uint16_t* zero;  // (bf16 only)
+  const void* x;         // NHWC [Nb][H][W][IC] (bf16 bits, or fp32 for wgrad3f_kernel)
+  const void* dy;        // NHWC [Nb][H][W][OC]
+  float* part;           // [splits][OC][Kg]
+  const void* zero;      // 16-byte zero page
   int H, W, log2w, IC, OC, Kg, npix;
   int n_c_tiles, n_oc_tiles, splits, steps_per_split;
   int pix;               // pixels per step (G: 56)
   FastDiv div_w, div_h;  // (G)
 };
-
-// wait until at most `ahead` later stage groups (PER DMA ops each) are still in flight
-template <int PER, int MAXA>
-PSX_DEV void wait_ahead(int ahead) {
-  if constexpr (MAXA <= 0) {
-    wait_vmcnt<0>();
-  } else {
-    if (ahead >= MAXA)
-      wait_vmcnt<MAXA * PER>();
-    else
-      wait_ahead<PER, MAXA - 1>(ahead);
-  }
-}
 
 template <int BC, int NS, bool G>
 __global__ __launch_bounds__(256) void wgrad3_kernel(Wgrad3Args a) {
@@ -405,6 +393,9 @@ __global__ __launch_bounds__(256) void wgrad3_kernel(Wgrad3Args a) {
   const int pbeg = split * a.steps_per_split * PIX;
   const int nsteps = min(a.steps_per_split, (a.npix - pbeg + PIX - 1) / PIX);
   const int W = a.W;
+  const uint16_t* const xg = (const uint16_t*)a.x;
+  const uint16_t* const dyg = (const uint16_t*)a.dy;
+  const uint16_t* const zero = (const uint16_t*)a.zero;
 
   // zero row (slot 64) of every stage; the DMA never writes it
   if (tid < NS * 8) *reinterpret_cast<uint4*>(smem + (tid >> 3) * STAGE + 64 * 128 + (tid & 7) * 16) = uint4{0, 0, 0, 0};
@@ -440,16 +431,16 @@ __global__ __launch_bounds__(256) void wgrad3_kernel(Wgrad3Args a) {
       } else {
         ih = ((pix >> a.log2w) & (a.H - 1)) + r - 1;
       }
-      const uint16_t* src = a.zero;
+      const uint16_t* src = zero;
       if ((!G || xrow[i] < PIX) && pix < a.npix && (unsigned)ih < (unsigned)a.H)
-        src = a.x + ((long)pix + xshift) * a.IC + xcol[i];
+        src = xg + ((long)pix + xshift) * a.IC + xcol[i];
       glds16(src, base + (i * 4 + wid) * 1024);
     }
 #pragma unroll
     for (int i = 0; i < LD; ++i) {
       const int pix = p0 + drow[i];
       const bool ok = (!G || drow[i] < PIX) && pix < a.npix;
-      const uint16_t* src = ok ? a.dy + (size_t)pix * a.OC + oc0 + dchunk[i] * 8 : a.zero;
+      const uint16_t* src = ok ? dyg + (size_t)pix * a.OC + oc0 + dchunk[i] * 8 : zero;
       glds16(src, base + XT + (i * 4 + wid) * 1024);
     }
   };
@@ -687,28 +678,114 @@ __global__ __launch_bounds__(256) void wgrad3f_kernel(Wgrad3Args a) {
 
 using namespace psx;
 
+extern "C" int psx_stem7_wgrad(const float* x, const float* dy, float* part, int Nb, int IH, int IW, int cin, int cp,
+                               int OC, int Kg, hipStream_t st);
+
 namespace {
 
-struct WPlan {
-  int BR, BC, NS, splits, sps;
+struct WGeom {
+  int Nb, H, W, IC, OC, R, S, stride, pad, Kg;
+  int OH() const { return (H + 2 * pad - R) / stride + 1; }
+  int OW() const { return (W + 2 * pad - S) / stride + 1; }
+  int npix() const { return Nb * OH() * OW(); }
+};
+
+// The launch decision of one weight gradient: which kernel family (kind, f32), which instantiation
+// (BR x BC tile, NS ring stages), how many splits of how many pixel-steps. Made once per call by
+// route_wgrad from the geometry alone; psx_conv_wgrad2 launches what it says and
+// psx_conv_wgrad2_path reports it, so the two cannot drift.
+enum { kTile = 0, kTap = 1, kTapG = 2, kStem7 = 3 };
+struct WRoute {
+  int kind;         // kTile wgrad2[f]_kernel, kTap / kTapG wgrad3[f]_kernel (G: general widths), kStem7 stem.hip
+  int f32;
+  int BR, BC, NS;   // tap reuse: BR = 192 (3 taps x 64 channels); stem7: 0
+  int splits, sps;  // sps: pixel-steps per split
+  int pix;          // pixels per step
 };
 
 // Workgroup slots of the chip the weight gradient plans for (256 CUs x occupancy).
 int wg_slots(int occ) { return 256 * occ; }
 
-// LDS bytes per workgroup of an NS-stage BR x BC tile (64 pixels per stage).
+// LDS bytes per workgroup: an NS-stage BR x BC tile of 64 bf16 / 32 fp32 pixels per stage, and the
+// tap-reuse tiles (x window of 64 channels + zero row / guard row, dy BC wide).
 constexpr int wlds(int BR, int BC, int NS) { return NS * 64 * (BR + BC) * 2; }
+constexpr int wldsf(int BR, int BC, int NS) { return NS * 32 * (BR + BC) * 4; }
+constexpr int wlds3(int BC, int NS) { return NS * (65 * 128 + 64 * BC * 2); }
+constexpr int wlds3f(int BC, int NS) { return NS * (256 + 32 * 256 + 32 * BC * 4); }
 
-// Occupancy-aware plan: tiles x splits workgroups should fill whole rounds of the
-// 256 CUs x (workgroups per CU that the LDS allows), with >= 8 pixel-steps per split; among
-// the tile shapes the one with the lowest modelled time wins (per-step costs measured on
-// MI355X with rocprofv3: 128x128 ~1.2 us at 1 WG/CU, 64x64 ~0.7 us at 3 WG/CU; +3 us
-// prologue/epilogue per workgroup; split-K partials cost a write + a read at ~5 TB/s).
-// fbr / fbc (> 0): only that tile (its split count still from the model).
-WPlan wplan(int OC, int Kg, int npix, int fbr = 0, int fbc = 0) {
-  WPlan best{64, 64, 3, 1, 0};
+// Workgroups per CU that the LDS allows, at most 3.
+int wocc(int lds) { return 163840 / lds > 3 ? 3 : 163840 / lds; }
+
+// One tile shape that a planner weighs: occ workgroups of it share a CU, `tiles` of them cover
+// dW, a pixel-step of one takes step_us. eff (fp32 model): MFMA efficiency at 1 / 2 / 3
+// co-resident workgroups.
+struct WCand {
+  int BR, BC, NS, occ;
+  long tiles;
+  double step_us;
+  const double* eff;
+};
+using WCost = double (*)(const WCand& c, int OC, int Kg, int spl, int sps);
+
+// bf16 round model: tiles x splits workgroups fill whole rounds of the 256 CUs x (workgroups per
+// CU that the LDS allows); +3 us prologue/epilogue per workgroup; split-K partials cost a write +
+// a read at ~5 TB/s.
+double wcost_bf16(const WCand& c, int OC, int Kg, int spl, int sps) {
+  const int slots = wg_slots(c.occ);
+  const long wgs = c.tiles * spl;
+  const long rounds = (wgs + slots - 1) / slots;
+  return rounds * (sps * c.step_us + 3.0) + (spl > 1 ? spl * (double)OC * Kg * 8.0 / 5e6 : 0.0);
+}
+
+// fp32 round model: workgroups run in rounds of 256 CUs x k co-resident workgroups (k <= the LDS
+// occupancy); a round's length is its workgroups' stages x the f32 MFMA time of a stage x
+// k / eff(k) — a lone wave per SIMD leaves every stage's DMA wait and barrier exposed — plus
+// ~1.5 us of prologue / partial-tile store, and the split-K partial traffic (written here, read by
+// the reduction) comes on top. Round quantisation dominates: the 64-channel 32x32 layer takes
+// 100 us at 84 splits (756 workgroups: one round at k = 3) and 131 us at 86 (774: a second round
+// for 6 workgroups).
+double wcost_f32(const WCand& c, int OC, int Kg, int spl, int sps) {
+  auto eff = [&](int k) { return c.eff[k <= 1 ? 0 : k == 2 ? 1 : 2]; };
+  const long wgs = c.tiles * spl, full = wgs / (256L * c.occ), rest = wgs - full * 256L * c.occ;
+  const int krest = (int)((rest + 255) / 256);
+  double t = full * (sps * c.step_us * c.occ / eff(c.occ) + 1.5);
+  if (rest) t += sps * c.step_us * krest / eff(krest) + 1.5;
+  if (spl > 1) t += spl * (double)OC * Kg * 6.0 / 6e6;  // reduction read + extra store
+  return t;
+}
+
+void wset(WRoute& r, int BR, int BC, int NS, int splits, int sps) {
+  r.BR = BR; r.BC = BC; r.NS = NS; r.splits = splits; r.sps = sps;
+}
+
+// The split search of every planner: sp = 1 .. smax pixel ranges of one candidate, the first
+// with the strictly lowest modelled time (over all candidates so far: best_t) goes into r.
+// equal: only split counts that give equal ranges (sp ranges of sps steps leave none empty; the
+// fp32 planners' filter).
+void wsearch(WRoute& r, double& best_t, const WCand& c, WCost cost, bool equal, int OC, int Kg, int steps, int smax) {
+  if (c.occ < 1) return;
+  for (int sp = 1; sp <= smax; ++sp) {
+    const int sps = (steps + sp - 1) / sp;
+    const int spl = (steps + sps - 1) / sps;
+    if (equal && sp > 1 && spl != sp) continue;
+    const double t = cost(c, OC, Kg, spl, sps);
+    if (t < best_t) {
+      best_t = t;
+      wset(r, c.BR, c.BC, c.NS, spl, sps);
+    }
+  }
+}
+
+// bf16 tile plan: >= 8 pixel-steps per split; among the tile shapes the one with the lowest
+// modelled time wins (per-step costs measured on MI355X with rocprofv3: 128x128 ~1.2 us at
+// 1 WG/CU, 64x64 ~0.7 us at 3 WG/CU). fbr / fbc (> 0): only that tile (its split count still from
+// the model). Split cap 256 (64 until round 6: ResNet-50's 56x56 1x1 layers sat at it with ~98
+// steps per workgroup; 256 measured -2 % on its bf16 step, profiles/r6_wgrad_split_cap_ab.jsonl).
+void wplan(WRoute& r, int OC, int Kg, int npix, int fbr, int fbc) {
+  wset(r, 64, 64, 3, 1, 0);
   double best_t = 1e30;
   const int steps = (npix + 63) / 64;
+  const int smax = steps / 8 > 0 ? steps / 8 : 1;
   const int brs[2] = {128, 64}, bcs[2] = {128, 64};
   for (int ib = 0; ib < 2; ++ib)
     for (int ic = 0; ic < 2; ++ic) {
@@ -716,89 +793,34 @@ WPlan wplan(int OC, int Kg, int npix, int fbr = 0, int fbc = 0) {
       if ((fbr && BR != fbr) || (fbc && BC != fbc)) continue;
       if (Kg % BR || OC % BC || (BR == 128 && Kg < 256)) continue;
       const int NS = (BR == 128 && BC == 128) ? 4 : 3;
-      int occ = 163840 / wlds(BR, BC, NS);
-      if (occ > 3) occ = 3;
-      if (occ < 1) continue;
-      const int slots = wg_slots(occ);
-      const long tiles = (long)(Kg / BR) * (OC / BC);
-      const double step_us = 0.55 + 0.15 * (double)(BR * BC) / 4096.0;
-      int smax = steps / 8 > 0 ? steps / 8 : 1;
-      // (cap 64 until round 6: ResNet-50's 56x56 1x1 layers sat at it with ~98 steps per
-      // workgroup; 256 measured -2 % on its bf16 step, profiles/r6_wgrad_split_cap_ab.jsonl)
-      for (int sp = 1; sp <= smax && sp <= 256; ++sp) {
-        const int sps = (steps + sp - 1) / sp;
-        const int spl = (steps + sps - 1) / sps;
-        const long wgs = tiles * spl;
-        const long rounds = (wgs + slots - 1) / slots;
-        const double t = rounds * (sps * step_us + 3.0) + (spl > 1 ? spl * (double)OC * Kg * 8.0 / 5e6 : 0.0);
-        if (t < best_t) {
-          best_t = t;
-          best = WPlan{BR, BC, NS, spl, sps};
-        }
-      }
+      const WCand c{BR, BC, NS, wocc(wlds(BR, BC, NS)), (long)(Kg / BR) * (OC / BC),
+                    0.55 + 0.15 * (double)(BR * BC) / 4096.0, nullptr};
+      wsearch(r, best_t, c, wcost_bf16, false, OC, Kg, steps, smax < 256 ? smax : 256);
     }
-  return best;
 }
 
-template <int BR, int BC, int NS>
-int launch_w2(const Wgrad2Args& a, hipStream_t st) {
-  const size_t lds = (size_t)wlds(BR, BC, NS);
-  hipLaunchKernelGGL((wgrad2_kernel<BR, BC, NS>), dim3(a.n_k_tiles * a.n_oc_tiles * a.splits), dim3(256), lds, st,
-                     a);
-  return (int)hipGetLastError();
-}
-
-constexpr int wlds3(int BC, int NS) { return NS * (65 * 128 + 64 * BC * 2); }
-
-// wgrad3 plan, same model as wplan with wgrad3's per-step costs.
-WPlan wplan3(int OC, int IC, int Kg, int npix, int pix = 64) {
-  WPlan best{0, 64, 3, 1, 0};
+// bf16 tap-reuse plan: the same model with wgrad3's per-step costs, >= 4 pixel-steps per split.
+// Split cap 128 (256 until round 6): fewer partial slabs to write and reduce; ResNet-18 bf16
+// -9.5 us twice, ResNet-50 bf16 -24 us, 64 +30 us (profiles/r6_wgrad3_split_cap_ab.jsonl).
+void wplan3(WRoute& r, int OC, int IC, int Kg, int npix, int pix) {
+  wset(r, 192, 64, 3, 1, 0);
   double best_t = 1e30;
   const int steps = npix / pix;
+  const int smax = steps / 4 > 0 ? steps / 4 : 1;
   for (int cfg = 0; cfg < 4; ++cfg) {
     const int BC = cfg & 1 ? 128 : 64, NS = cfg & 2 ? 6 : 3;
     if (OC % BC) continue;
-    int occ = 163840 / wlds3(BC, NS);
-    if (occ > 3) occ = 3;
-    if (occ < 1) continue;
-    const int slots = wg_slots(occ);
-    const long tiles = 3L * (IC / 64) * (OC / BC);
-    const double step_us = (BC == 64 ? 0.9 : 1.3) * (NS == 6 ? 0.8 : 1.0);
-    const int smax = steps / 4 > 0 ? steps / 4 : 1;
-    // split cap 128 (256 until round 6): fewer partial slabs to write and reduce; ResNet-18 bf16
-    // -9.5 us twice, ResNet-50 bf16 -24 us, 64 +30 us (profiles/r6_wgrad3_split_cap_ab.jsonl)
-    for (int sp = 1; sp <= smax && sp <= 128; ++sp) {
-      const int sps = (steps + sp - 1) / sp;
-      const int spl = (steps + sps - 1) / sps;
-      const long wgs = tiles * spl;
-      const long rounds = (wgs + slots - 1) / slots;
-      const double t = rounds * (sps * step_us + 3.0) + (spl > 1 ? spl * (double)OC * Kg * 8.0 / 5e6 : 0.0);
-      if (t < best_t) {
-        best_t = t;
-        best = WPlan{0, BC, NS, spl, sps};
-      }
-    }
+    const WCand c{192, BC, NS, wocc(wlds3(BC, NS)), 3L * (IC / 64) * (OC / BC),
+                  (BC == 64 ? 0.9 : 1.3) * (NS == 6 ? 0.8 : 1.0), nullptr};
+    wsearch(r, best_t, c, wcost_bf16, false, OC, Kg, steps, smax < 128 ? smax : 128);
   }
-  return best;
 }
 
-template <int BC, int NS, bool G = false>
-int launch_w3(const Wgrad3Args& a, hipStream_t st) {
-  hipLaunchKernelGGL((wgrad3_kernel<BC, NS, G>), dim3(3 * a.n_c_tiles * a.n_oc_tiles * a.splits), dim3(256),
-                     (size_t)wlds3(BC, NS), st, a);
-  return (int)hipGetLastError();
-}
-
-// fp32 plan (wgrad2f_kernel): workgroups run in rounds of 256 CUs x k co-resident workgroups
-// (k <= the LDS occupancy); a round's length is its workgroups' stages x the f32 MFMA time of a
-// stage (BR*BC/4 cycles per wave) x k / eff(k) — a lone wave per SIMD leaves every stage's DMA wait
-// and barrier exposed — plus ~1.5 us of prologue / partial-tile store, and the split-K partial
-// traffic (written here, read by the reduction) comes on top. Round quantisation dominates: the
-// 64-channel 32x32 layer takes 100 us at 84 splits (756 workgroups: one round at k = 3) and 131 us
-// at 86 (774: a second round for 6 workgroups). eff measured with scripts/dev/wgf_splits.py:
-// 64x64 0.55 / 0.65 / 0.72 at k = 1 / 2 / 3.
-WPlan wplanf(int OC, int Kg, int npix) {
-  WPlan best{64, 64, 3, 1, 0};
+// fp32 tile plan (wgrad2f_kernel): a stage at the full f32 MFMA rate is BR*BC/4 cycles per wave;
+// eff as measured: 64x64 0.55 / 0.65 / 0.72 at k = 1 / 2 / 3 co-resident workgroups.
+void wplanf(WRoute& r, int OC, int Kg, int npix) {
+  static const double eff_sq[3] = {0.55, 0.65, 0.72}, eff_wide[3] = {0.60, 0.68, 0.68};
+  wset(r, 64, 64, 3, 1, 0);
   double best_t = 1e30;
   const int steps = (npix + 31) / 32;
   const int brs[2] = {128, 64}, bcs[2] = {128, 64};
@@ -806,86 +828,148 @@ WPlan wplanf(int OC, int Kg, int npix) {
     for (int ic = 0; ic < 2; ++ic) {
       const int BR = brs[ib], BC = bcs[ic];
       if (Kg % BR || OC % BC) continue;
-      const int NS = 3;
-      int occ = 163840 / (NS * 32 * (BR + BC) * 4);
-      if (occ > 3) occ = 3;
-      if (occ < 1) continue;
-      const bool sq = BR == 64 && BC == 64;
-      const long tiles = (long)(Kg / BR) * (OC / BC);
-      const double step_us = (double)(BR * BC) / 4.0 / 2100.0;  // one stage at full f32 MFMA rate
-      auto eff = [&](int k) { return sq ? (k <= 1 ? 0.55 : k == 2 ? 0.65 : 0.72) : (k <= 1 ? 0.60 : 0.68); };
-      for (int sp = 1; sp <= 256 && sp <= steps; ++sp) {
-        const int sps = (steps + sp - 1) / sp;
-        const int spl = (steps + sps - 1) / sps;
-        if (sp > 1 && spl != sp) continue;
-        const long wgs = tiles * spl, full = wgs / (256L * occ), rest = wgs - full * 256L * occ;
-        const int krest = (int)((rest + 255) / 256);
-        double t = full * (sps * step_us * occ / eff(occ) + 1.5);
-        if (rest) t += sps * step_us * krest / eff(krest) + 1.5;
-        if (spl > 1) t += spl * (double)OC * Kg * 6.0 / 6e6;  // reduction read + extra store
-        if (t < best_t) {
-          best_t = t;
-          best = WPlan{BR, BC, NS, spl, sps};
-        }
-      }
+      const WCand c{BR, BC, 3, wocc(wldsf(BR, BC, 3)), (long)(Kg / BR) * (OC / BC),
+                    (double)(BR * BC) / 4.0 / 2100.0, BR == 64 && BC == 64 ? eff_sq : eff_wide};
+      wsearch(r, best_t, c, wcost_f32, true, OC, Kg, steps, steps < 256 ? steps : 256);
     }
-  return best;
 }
 
-constexpr int wlds3f(int BC, int NS) { return NS * (256 + 32 * 256 + 32 * BC * 4); }
-
-// wgrad3f plan: the wplanf round model with the tap-reuse tile (192 x BC per workgroup, 3 x 64 x
-// BC x 32 MACs per stage). eff(k) as measured for the tap-reuse conv mainloops (64-66 % at 2-3
-// co-resident workgroups).
-WPlan wplan3f(int OC, int IC, int Kg, int npix) {
-  WPlan best{0, 64, 3, 1, 0};
+// fp32 tap-reuse plan (wgrad3f_kernel): the fp32 round model with the tap-reuse tile (192 x BC
+// per workgroup, 3 x 64 x BC x 32 MACs per stage). eff(k) as measured for the tap-reuse conv
+// mainloops (64-66 % at 2-3 co-resident workgroups).
+void wplan3f(WRoute& r, int OC, int IC, int Kg, int npix) {
+  static const double eff[3] = {0.55, 0.66, 0.70};
+  wset(r, 192, 64, 3, 1, 0);
   double best_t = 1e30;
   const int steps = npix / 32;
   for (int BC = 64; BC <= 128; BC *= 2) {
     if (OC % BC) continue;
-    const int NS = 3;
-    int occ = 163840 / wlds3f(BC, NS);
-    if (occ > 3) occ = 3;
-    const long tiles = 3L * (IC / 64) * (OC / BC);
-    const double step_us = 3.0 * 64 * BC / 4.0 / 2100.0;
-    auto eff = [&](int k) { return k <= 1 ? 0.55 : k == 2 ? 0.66 : 0.70; };
-    for (int sp = 1; sp <= 512 && sp <= steps; ++sp) {
-      const int sps = (steps + sp - 1) / sp;
-      const int spl = (steps + sps - 1) / sps;
-      if (sp > 1 && spl != sp) continue;
-      const long wgs = tiles * spl, full = wgs / (256L * occ), rest = wgs - full * 256L * occ;
-      const int krest = (int)((rest + 255) / 256);
-      double t = full * (sps * step_us * occ / eff(occ) + 1.5);
-      if (rest) t += sps * step_us * krest / eff(krest) + 1.5;
-      if (spl > 1) t += spl * (double)OC * Kg * 6.0 / 6e6;
-      if (t < best_t) {
-        best_t = t;
-        best = WPlan{0, BC, NS, spl, sps};
-      }
+    const WCand c{192, BC, 3, wocc(wlds3f(BC, 3)), 3L * (IC / 64) * (OC / BC), 3.0 * 64 * BC / 4.0 / 2100.0, eff};
+    wsearch(r, best_t, c, wcost_f32, true, OC, Kg, steps, steps < 512 ? steps : 512);
+  }
+}
+
+// Which kernel the weight gradient of this geometry takes and how it is split; 0, or the code
+// psx_conv_wgrad2 refuses the geometry with (-2).
+int route_wgrad(const WGeom& g, bool f32, WRoute& r) {
+  const int H = g.H, W = g.W, IC = g.IC, OC = g.OC, Kg = g.Kg, npix = g.npix();
+  r = WRoute{kTile, f32 ? 1 : 0, 0, 0, 0, 1, 0, 0};
+  if (OC % 64 || Kg % 64) return -2;
+  if (f32 && IC == 4 && g.R == 7 && g.S == 7 && g.stride == 2 && g.pad == 3 && OC == 64 && H == 224 && W == 224) {
+    // the ImageNet stem: its own MFMA kernel with the input patch in LDS (stem.hip), its own split query
+    const int e = psx_stem7_wgrad(nullptr, nullptr, nullptr, g.Nb, H, W, 3, 4, OC, Kg, nullptr);
+    if (e != -11) {
+      r.kind = kStem7;
+      r.splits = e;
+      return e < 0 ? e : 0;
     }
   }
-  return best;
-}
-
-template <int BC>
-int launch_w3f(const Wgrad3Args& a, hipStream_t st) {
-  hipLaunchKernelGGL((wgrad3f_kernel<BC, 3>), dim3(3 * a.n_c_tiles * a.n_oc_tiles * a.splits), dim3(256),
-                     (size_t)wlds3f(BC, 3), st, a);
-  return (int)hipGetLastError();
-}
-
-template <int BR, int BC>
-int launch_w2f(const Wgrad2Args& a, hipStream_t st) {
-  const size_t lds = (size_t)3 * 32 * (BR + BC) * 4;
-  hipLaunchKernelGGL((wgrad2f_kernel<BR, BC, 3>), dim3(a.n_k_tiles * a.n_oc_tiles * a.splits), dim3(256), lds, st,
-                     a);
-  return (int)hipGetLastError();
+  // 3x3 stride-1 layers, tap-reuse kernels: power-of-two rows (whole rows in 64-pixel steps, 32 in
+  // fp32), or in bf16 widths dividing 56 (ResNet-50: 56-pixel steps of whole rows, G)
+  const bool w3ok = g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && IC % 64 == 0;
+  const bool pow2hw = (W & (W - 1)) == 0 && (H & (H - 1)) == 0 && W >= 2;
+  if (f32 && w3ok && pow2hw && W <= 32 && npix % 32 == 0 && Kg == 9 * IC) {
+    r.kind = kTap;
+    r.pix = 32;
+    wplan3f(r, OC, IC, Kg, npix);
+  } else if (f32) {
+    if (IC % 4 || (IC & (IC - 1))) return -2;
+    r.pix = 32;
+    wplanf(r, OC, Kg, npix);
+  } else {
+    const bool pow2 = pow2hw && W <= 64 && npix % 64 == 0;
+    const bool gen = !pow2 && W >= 2 && 56 % W == 0 && npix % 56 == 0;
+    if (w3ok && (pow2 || gen)) {
+      r.kind = pow2 ? kTap : kTapG;
+      r.pix = pow2 ? 64 : 56;
+      wplan3(r, OC, IC, Kg, npix, r.pix);
+    } else {
+      // Tile: the round-5 sweep (profiles/r5_r50_wgrad_tiles.jsonl, ResNet-50's 1x1 layers): 64 (k) x
+      // 128 (oc) wins by 10-20 % on every layer up to 28x28 with OC % 128 == 0 (128x512x28 42.0 ->
+      // 34.7 us, 1024x2048x14/s2 64.3 -> 55.4), 64x64 on the 56x56 ones (the model's choice there).
+      const bool t128 = OC % 128 == 0 && Kg % 64 == 0 && npix <= 128 * 28 * 28;
+      r.pix = 64;
+      wplan(r, OC, Kg, npix, t128 ? 64 : 0, t128 ? 128 : 0);
+    }
+  }
+  if ((r.kind == kTile && Kg % r.BR) || OC % r.BC) return -2;
+  return 0;
 }
 
 int ilog2w(int v) {
   int l = 0;
   while ((1 << l) < v) ++l;
   return l;
+}
+
+// One launch table per kernel family: every instantiation, by the route fields that select it.
+// (Listed in the order the file has always instantiated them: the compiler numbers its local
+// labels by that order, so scripts/prof/isa_equal.py sees any reordering as a change.)
+template <typename Args>
+struct WKernel {
+  int kind, BR, BC, NS;
+  void (*fn)(Args);
+  int lds;
+};
+#define PSX_W2F(BR, BC) {kTile, BR, BC, 3, wgrad2f_kernel<BR, BC, 3>, wldsf(BR, BC, 3)}
+#define PSX_W3F(BC) {kTap, 192, BC, 3, wgrad3f_kernel<BC, 3>, wlds3f(BC, 3)}
+#define PSX_W3(BC, NS, G) {G ? kTapG : kTap, 192, BC, NS, wgrad3_kernel<BC, NS, G>, wlds3(BC, NS)}
+#define PSX_W2(BR, BC, NS) {kTile, BR, BC, NS, wgrad2_kernel<BR, BC, NS>, wlds(BR, BC, NS)}
+const WKernel<Wgrad2Args> kW2fKernels[4] = {PSX_W2F(128, 128), PSX_W2F(128, 64), PSX_W2F(64, 128), PSX_W2F(64, 64)};
+const WKernel<Wgrad3Args> kW3fKernels[2] = {PSX_W3F(128), PSX_W3F(64)};
+const WKernel<Wgrad3Args> kW3Kernels[8] = {PSX_W3(128, 6, false), PSX_W3(128, 3, false), PSX_W3(64, 6, false),
+                                           PSX_W3(64, 3, false),  PSX_W3(128, 6, true),  PSX_W3(128, 3, true),
+                                           PSX_W3(64, 6, true),   PSX_W3(64, 3, true)};
+const WKernel<Wgrad2Args> kW2Kernels[4] = {PSX_W2(128, 128, 4), PSX_W2(128, 64, 3), PSX_W2(64, 128, 3),
+                                           PSX_W2(64, 64, 3)};
+#undef PSX_W2F
+#undef PSX_W3F
+#undef PSX_W3
+#undef PSX_W2
+
+// Launches the route's kernel of an n-entry table over tiles x splits workgroups; returns the HIP error code.
+template <typename Args>
+int wlaunch(const WKernel<Args>* tab, int n, const WRoute& r, int tiles, const Args& a, hipStream_t st) {
+  for (const WKernel<Args>* k = tab; k < tab + n; ++k)
+    if (k->kind == r.kind && k->BR == r.BR && k->BC == r.BC && k->NS == r.NS) {
+      hipLaunchKernelGGL(k->fn, dim3(tiles * r.splits), dim3(256), (size_t)k->lds, st, a);
+      return (int)hipGetLastError();
+    }
+  return (int)hipErrorInvalidDeviceFunction;  // no such instantiation
+}
+
+int launch_tile(const WRoute& r, const WGeom& g, const void* x, const void* dy, float* part, const void* zero,
+                hipStream_t st) {
+  Wgrad2Args a{};
+  a.x = x;
+  a.dy = dy;
+  a.part = part;
+  a.zero = zero;
+  a.IH = g.H; a.IW = g.W; a.IC = g.IC; a.OC = g.OC; a.R = g.R; a.S = g.S; a.pad = g.pad; a.stride = g.stride;
+  a.Kg = g.Kg;
+  a.log2_icc = ilog2w(g.IC / (r.f32 ? 4 : 8));
+  a.npix = g.npix();
+  a.div_ohw = make_fastdiv(g.OH() * g.OW());
+  a.div_ow = make_fastdiv(g.OW());
+  a.div_s = make_fastdiv(g.S);
+  a.n_k_tiles = g.Kg / r.BR;
+  a.n_oc_tiles = g.OC / r.BC;
+  a.splits = r.splits;
+  a.steps_per_split = r.sps;
+  return wlaunch(r.f32 ? kW2fKernels : kW2Kernels, 4, r, a.n_k_tiles * a.n_oc_tiles, a, st);
+}
+
+int launch_tap(const WRoute& r, const WGeom& g, const void* x, const void* dy, float* part, const void* zero,
+               hipStream_t st) {
+  Wgrad3Args b{};
+  b.x = x; b.dy = dy; b.part = part; b.zero = zero;
+  b.H = g.H; b.W = g.W; b.log2w = ilog2w(g.W); b.IC = g.IC; b.OC = g.OC; b.Kg = g.Kg; b.npix = g.npix();
+  b.n_c_tiles = g.IC / 64; b.n_oc_tiles = g.OC / r.BC; b.splits = r.splits; b.steps_per_split = r.sps;
+  b.pix = r.pix;
+  b.div_w = make_fastdiv(g.W);
+  b.div_h = make_fastdiv(g.H);
+  return r.f32 ? wlaunch(kW3fKernels, 2, r, 3 * b.n_c_tiles * b.n_oc_tiles, b, st)
+               : wlaunch(kW3Kernels, 8, r, 3 * b.n_c_tiles * b.n_oc_tiles, b, st);
 }
 
 }  // namespace
@@ -900,129 +984,35 @@ int psx_bgemm_tn_f32(const float* X, const float* D, float* part, const void* ze
                      int BR, int BC, hipStream_t st) {
   if (q < 1 || T % (32 * q) || C % BR || K % BC || (C & (C - 1)) || (BR != 64 && BR != 128) || (BC != 64 && BC != 128))
     return -2;
-  Wgrad2Args a{};
-  a.x = X;
-  a.dy = D;
-  a.part = part;
-  a.zero = zero;
-  a.IH = a.IW = 1; a.IC = C; a.OC = K; a.R = a.S = 1; a.pad = 0; a.stride = 1;
-  a.Kg = C;
-  a.log2_icc = ilog2w(C / 4);
-  a.npix = nb * T;
-  a.div_ohw = make_fastdiv(1);
-  a.div_ow = make_fastdiv(1);
-  a.div_s = make_fastdiv(1);
-  a.n_k_tiles = C / BR;
-  a.n_oc_tiles = K / BC;
-  a.splits = nb * q;
-  a.steps_per_split = T / q / 32;
-  if (BR == 128 && BC == 128) return launch_w2f<128, 128>(a, st);
-  if (BR == 128) return launch_w2f<128, 64>(a, st);
-  if (BC == 128) return launch_w2f<64, 128>(a, st);
-  return launch_w2f<64, 64>(a, st);
+  const WGeom g{nb * T, 1, 1, C, K, 1, 1, 1, 0, C};
+  const WRoute r{kTile, 1, BR, BC, 3, nb * q, T / q / 32, 32};
+  return launch_tile(r, g, X, D, part, zero, st);
+}
+
+// Which kernel psx_conv_wgrad2 launches for this geometry and how it splits the pixels, without
+// launching anything: route_wgrad's decision. out[8]: kind (0 tile, 1 tap reuse, 2 tap reuse over
+// general widths, 3 the ImageNet stem), f32, BR, BC, NS, splits, pixel-steps per split, pixels
+// per step. Returns 0 or psx_conv_wgrad2's own refusal of the geometry (-2).
+int psx_conv_wgrad2_path(int Nb, int H, int W, int IC, int OC, int R, int S, int stride, int pad, int Kg, int f32,
+                         int* out) {
+  WRoute r;
+  if (const int e = route_wgrad(WGeom{Nb, H, W, IC, OC, R, S, stride, pad, Kg}, f32 != 0, r)) return e;
+  const int v[8] = {r.kind, r.f32, r.BR, r.BC, r.NS, r.splits, r.sps, r.pix};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  return 0;
 }
 
 // Returns the split count (query with part == nullptr); partials need splits*OC*Kg floats.
 // f32: x / dy are fp32 (wgrad2f_kernel) instead of bf16.
-extern "C" int psx_stem7_wgrad(const float* x, const float* dy, float* part, int Nb, int IH, int IW, int cin, int cp,
-                               int OC, int Kg, hipStream_t st);
-
 int psx_conv_wgrad2(const void* x, const void* dy, float* part, const void* zero, int Nb, int H, int W, int IC, int OC,
                     int R, int S, int stride, int pad, int Kg, int f32, hipStream_t st) {
-  Wgrad2Args a{};
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
-  a.x = x;
-  a.dy = dy;
-  a.part = part;
-  a.zero = zero;
-  a.IH = H; a.IW = W; a.IC = IC; a.OC = OC; a.R = R; a.S = S; a.pad = pad; a.stride = stride;
-  a.Kg = Kg;
-  a.log2_icc = ilog2w(IC / 8);
-  a.npix = Nb * OH * OW;
-  a.div_ohw = make_fastdiv(OH * OW);
-  a.div_ow = make_fastdiv(OW);
-  a.div_s = make_fastdiv(S);
-  if (OC % 64 || Kg % 64) return -2;
-  if (f32 && IC == 4 && R == 7 && S == 7 && stride == 2 && pad == 3 && OC == 64 && H == 224 && W == 224) {
-    // the ImageNet stem: its own MFMA kernel with the input patch in LDS (stem.hip)
-    const int e = psx_stem7_wgrad((const float*)x, (const float*)dy, part, Nb, H, W, 3, 4, OC, Kg, st);
-    if (e != -11) return e;
-  }
-  const bool w3ok = R == 3 && S == 3 && stride == 1 && pad == 1 && IC % 64 == 0;
-  if (f32 && w3ok && (W & (W - 1)) == 0 && (H & (H - 1)) == 0 && W <= 32 && W >= 2 && a.npix % 32 == 0 &&
-      Kg == 9 * IC) {
-    // 3x3 stride-1 layers: fp32 tap-reuse kernel
-    WPlan p = wplan3f(OC, IC, Kg, a.npix);
-    if (OC % p.BC) return -2;
-    if (!part) return p.splits;
-    Wgrad3Args b{};
-    b.x = (const uint16_t*)x; b.dy = (const uint16_t*)dy; b.part = part; b.zero = (const uint16_t*)zero;
-    b.H = H; b.W = W; b.log2w = ilog2w(W); b.IC = IC; b.OC = OC; b.Kg = Kg; b.npix = a.npix;
-    b.n_c_tiles = IC / 64; b.n_oc_tiles = OC / p.BC; b.splits = p.splits; b.steps_per_split = p.sps;
-    b.pix = 32;
-    const int e = p.BC == 128 ? launch_w3f<128>(b, st) : launch_w3f<64>(b, st);
-    return e ? -e : p.splits;
-  }
-  if (f32) {
-    a.log2_icc = ilog2w(IC / 4);
-    if (IC % 4 || (IC & (IC - 1))) return -2;
-    WPlan p = wplanf(OC, Kg, a.npix);
-    if (Kg % p.BR || OC % p.BC) return -2;
-    a.n_k_tiles = Kg / p.BR;
-    a.n_oc_tiles = OC / p.BC;
-    a.splits = p.splits;
-    a.steps_per_split = p.sps;
-    if (!part) return p.splits;
-    int e;
-    if (p.BR == 128 && p.BC == 128) e = launch_w2f<128, 128>(a, st);
-    else if (p.BR == 128) e = launch_w2f<128, 64>(a, st);
-    else if (p.BC == 128) e = launch_w2f<64, 128>(a, st);
-    else e = launch_w2f<64, 64>(a, st);
-    return e ? -e : p.splits;
-  }
-  // 3x3 stride-1 layers, tap-reuse kernel: power-of-two rows (64-pixel
-  // steps), or widths dividing 56 (ResNet-50: 56-pixel steps of whole rows, G)
-  const bool pow2 = (W & (W - 1)) == 0 && (H & (H - 1)) == 0 && W <= 64 && W >= 2 && a.npix % 64 == 0;
-  const bool gen = !pow2 && W >= 2 && 56 % W == 0 && a.npix % 56 == 0;
-  if (w3ok && (pow2 || gen)) {
-    const int pix = pow2 ? 64 : 56;
-    WPlan p = wplan3(OC, IC, Kg, a.npix, pix);
-    if (OC % p.BC) return -2;
-    if (!part) return p.splits;
-    Wgrad3Args b{};
-    b.x = (const uint16_t*)a.x; b.dy = (const uint16_t*)a.dy; b.part = part; b.zero = (const uint16_t*)a.zero;
-    b.H = H; b.W = W; b.log2w = ilog2w(W); b.IC = IC; b.OC = OC; b.Kg = Kg; b.npix = a.npix;
-    b.n_c_tiles = IC / 64; b.n_oc_tiles = OC / p.BC; b.splits = p.splits; b.steps_per_split = p.sps;
-    b.pix = pix;
-    b.div_w = make_fastdiv(W);
-    b.div_h = make_fastdiv(H);
-    int e;
-    if (pow2)
-      e = p.BC == 128 ? (p.NS == 6 ? launch_w3<128, 6>(b, st) : launch_w3<128, 3>(b, st))
-                      : (p.NS == 6 ? launch_w3<64, 6>(b, st) : launch_w3<64, 3>(b, st));
-    else
-      e = p.BC == 128 ? (p.NS == 6 ? launch_w3<128, 6, true>(b, st) : launch_w3<128, 3, true>(b, st))
-                      : (p.NS == 6 ? launch_w3<64, 6, true>(b, st) : launch_w3<64, 3, true>(b, st));
-    return e ? -e : p.splits;
-  }
-  // Tile: the round-5 sweep (bench/r50_wgrad_tiles.py, profiles/r5_r50_wgrad_tiles.jsonl, ResNet-50's
-  // 1x1 layers): 64 (k) x 128 (oc) wins by 10-20 % on every layer up to 28x28 with OC % 128 == 0
-  // (128x512x28 42.0 -> 34.7 us, 1024x2048x14/s2 64.3 -> 55.4), 64x64 on the 56x56 ones (the
-  // model's choice there).
-  const bool t128 = OC % 128 == 0 && Kg % 64 == 0 && a.npix <= 128 * 28 * 28;
-  WPlan p = t128 ? wplan(OC, Kg, a.npix, 64, 128) : wplan(OC, Kg, a.npix);
-  if (Kg % p.BR || OC % p.BC) return -2;
-  a.n_k_tiles = Kg / p.BR;
-  a.n_oc_tiles = OC / p.BC;
-  a.splits = p.splits;
-  a.steps_per_split = p.sps;
-  if (!part) return p.splits;
-  int e;
-  if (p.BR == 128 && p.BC == 128) e = launch_w2<128, 128, 4>(a, st);
-  else if (p.BR == 128) e = launch_w2<128, 64, 3>(a, st);
-  else if (p.BC == 128) e = launch_w2<64, 128, 3>(a, st);
-  else e = launch_w2<64, 64, 3>(a, st);
-  return e ? -e : p.splits;
+  const WGeom g{Nb, H, W, IC, OC, R, S, stride, pad, Kg};
+  WRoute r;
+  if (const int e = route_wgrad(g, f32 != 0, r)) return e;
+  if (!part) return r.splits;
+  if (r.kind == kStem7) return psx_stem7_wgrad((const float*)x, (const float*)dy, part, Nb, H, W, 3, 4, OC, Kg, st);
+  const int e = r.kind == kTile ? launch_tile(r, g, x, dy, part, zero, st) : launch_tap(r, g, x, dy, part, zero, st);
+  return e ? -e : r.splits;
 }
 
 }  // extern "C"

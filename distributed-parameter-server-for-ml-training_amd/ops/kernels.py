@@ -385,6 +385,23 @@ def wino_wgrad_fused(x, dy, part, out, nb, h, w, c, k, scale=1.0, xaff=None, bwd
           "wino_wgrad_fused")
 
 
+WGRAD2_KINDS = ("tile", "tap_reuse", "tap_reuse_general", "stem7")
+
+
+def conv_wgrad2_path(nb, h, w, ic, oc, k, stride, pad, kg, f32=False):
+    """Which kernel conv_wgrad2 would launch for this geometry and how it splits the pixels, on the
+    host alone (csrc/kernels/wgrad_v2.hip psx_conv_wgrad2_path: the launch's own decision). Returns
+    a dict: kind (one of WGRAD2_KINDS), f32, br, bc, ns (the instantiation: tile and ring stages;
+    br = 192 for the tap-reuse kernels, 0 for the stem's), splits, kps (pixel-steps per split), pix
+    (pixels per step); or the negative code conv_wgrad2 would refuse the geometry with (-2)."""
+    out = (C.c_int * 8)()
+    rc = int(kernels().psx_conv_wgrad2_path(nb, h, w, ic, oc, k, k, stride, pad, kg, int(bool(f32)), out))
+    if rc:
+        return rc
+    v = list(out)
+    return dict(kind=WGRAD2_KINDS[v[0]], f32=bool(v[1]), br=v[2], bc=v[3], ns=v[4], splits=v[5], kps=v[6], pix=v[7])
+
+
 def conv_wgrad2_splits(nb, h, w, ic, oc, k, stride, pad, kg, f32=False) -> int:
     n = kernels().psx_conv_wgrad2(None, None, None, None, nb, h, w, ic, oc, k, k, stride, pad, kg, int(bool(f32)), None)
     if n <= 0:

@@ -27,7 +27,8 @@ CUID = re.compile(r"__hip_cuid_[0-9a-f]+")
 FUNC = re.compile(r"^\s*\.type\s+([^\s,]+),@function")
 KERNEL = re.compile(r"^\s*\.amdhsa_kernel\s+(\S+)")
 TAIL_AT = re.compile(r"^\s*\.(type\s+[^\s,]+,@object|amdgpu_metadata)\b")
-HEAD, TAIL = "<head>", "<tail>"
+LEAD = re.compile(r"^\s*\.(section|protected|globl|weak|hidden|p2align)\b")
+HEAD, TAIL ="<head>", "<tail>"
 
 
 def normalise(text: str) -> str:
@@ -39,17 +40,21 @@ def split_symbols(text: str) -> tuple[dict, set]:
     symbol's text runs from its '.type S,@function' line to the next one: the code, for a kernel
     the descriptor that follows it (.amdhsa_kernel .. .end_amdhsa_kernel, the register and LDS
     budget) and the compiler's resource comments. What precedes the first symbol is HEAD; from the
-    first variable ('.type V,@object') or the metadata note on, all is TAIL. (The few directives in
-    front of a '.type' line go with the symbol before it: a symbol that one side lacks marks its
-    predecessor different as well.)"""
+    first variable ('.type V,@object') or the metadata note on, all is TAIL. The directives right in
+    front of a '.type' line (.section / .protected / .globl / .p2align ...) name the symbol that
+    follows and go with it, so symbols compare equal in whatever order the two files define them."""
     parts, kernels, name = {HEAD: []}, set(), HEAD
     for line in text.splitlines():
         m = FUNC.match(line)
         if name != TAIL and m:
-            name = m.group(1)
+            prev, name = parts[name], m.group(1)
             if name in parts:
                 raise ValueError(f"symbol {name} defined twice")
-            parts[name] = []
+            n = len(prev)
+            while n and LEAD.match(prev[n - 1]):
+                n -= 1
+            parts[name] = prev[n:]
+            del prev[n:]
         elif name != TAIL and TAIL_AT.match(line):
             name = TAIL
             parts[name] = []

@@ -47,10 +47,22 @@ def test_conv_fwd2(shape):
     assert torch.allclose(stats[:, 1].sum(0), (yq * yq).sum(0), rtol=1e-3, atol=5e-2), shape
 
 
-@pytest.mark.parametrize("shape", SHAPES)
+# Weight-gradient kernels that the planner takes for no layer above: the smallest shape of a search
+# with K.conv_wgrad2_path that takes each -> the (kind, br, bc, ns) it must report. The general-width
+# tap-reuse kernel with the 3-stage ring twice: its smallest shape ends after two steps, the other
+# one runs the ring round (7 steps per split) over 4 splits.
+WGRAD_ROUTES = {(59, 512, 64, 14, 3, 1, 1): ("tile", 128, 64, 3),                  # wgrad2_kernel<128,64,3>
+                (7, 512, 1024, 4, 3, 1, 1): ("tap_reuse_general", 192, 64, 3),    # wgrad3_kernel<64,3,true>
+                (2, 256, 512, 28, 3, 1, 1): ("tap_reuse_general", 192, 64, 3)}
+
+
+@pytest.mark.parametrize("shape", SHAPES + list(WGRAD_ROUTES))
 def test_conv_wgrad2(shape):
     torch.manual_seed(2)
     n, cin, cout, hw, k, s, p = shape
+    if shape in WGRAD_ROUTES:
+        path = K.conv_wgrad2_path(n, hw, hw, cin, cout, k, s, p, k * k * cin)
+        assert (path["kind"], path["br"], path["bc"], path["ns"]) == WGRAD_ROUTES[shape], path
     x = torch.randn(n, cin, hw, hw, device=DEV).to(torch.bfloat16).float()
     oh = (hw + 2 * p - k) // s + 1
     dy = torch.randn(n, cout, oh, oh, device=DEV).to(torch.bfloat16).float()
@@ -63,6 +75,19 @@ def test_conv_wgrad2(shape):
     out = torch.zeros(cout * cin * k * k, device=DEV)
     K.wgrad_reduce(part, splits, cout, kg, cin, cp, k, 1.0, out.data_ptr(), False)
     assert _rel(out.view_as(ref), ref) < 5e-3, shape
+
+
+def test_conv_wgrad2_shapes_reach_every_route():
+    """test_conv_wgrad2's list takes every bf16 kernel that the planner is known to choose
+    (profiles/wgrad_routes.txt); host query only."""
+    reached = set()
+    for n, cin, cout, hw, k, s, p in SHAPES + list(WGRAD_ROUTES):
+        cp = _pow2(cin)
+        path = K.conv_wgrad2_path(n, hw, hw, cp, cout, k, s, p, -(-(k * k * cp) // 64) * 64)
+        reached.add((path["kind"], path["br"], path["bc"], path["ns"]))
+    assert reached == {("tile", 64, 64, 3), ("tile", 64, 128, 3), ("tile", 128, 64, 3), ("tap_reuse", 192, 64, 3),
+                       ("tap_reuse", 192, 64, 6), ("tap_reuse_general", 192, 64, 3),
+                       ("tap_reuse_general", 192, 64, 6)}
 
 
 @pytest.mark.parametrize("shape", [s for s in SHAPES if s[1] != 3])

@@ -42,8 +42,17 @@ def test_bgemm_f32(m, n, kd, nb, cfg):
     assert _rel(p, ref) < TOL
 
 
-@pytest.mark.parametrize("t,c,k,nb,q,br,bc", [(64, 64, 64, 3, 1, 64, 64), (512, 128, 256, 36, 2, 128, 128),
-                                              (128, 512, 64, 5, 4, 128, 64), (96, 64, 128, 2, 3, 64, 128)])
+BGEMM_TN = [(64, 64, 64, 3, 1, 64, 64), (512, 128, 256, 36, 2, 128, 128), (128, 512, 64, 5, 4, 128, 64),
+            (96, 64, 128, 2, 3, 64, 128)]
+
+
+def test_bgemm_tn_f32_drives_every_tile():
+    """The list below launches all four wgrad2f_kernel tiles (psx_bgemm_tn_f32 takes the tile as an
+    argument; the weight-gradient planner itself picks the wide ones almost nowhere)."""
+    assert {(br, bc) for *_, br, bc in BGEMM_TN} == {(64, 64), (64, 128), (128, 64), (128, 128)}
+
+
+@pytest.mark.parametrize("t,c,k,nb,q,br,bc", BGEMM_TN)
 def test_bgemm_tn_f32(t, c, k, nb, q, br, bc):
     torch.manual_seed(t + c + k)
     x = torch.randn(nb, t, c, device=DEV)
