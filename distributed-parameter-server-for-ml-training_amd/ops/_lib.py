@@ -106,6 +106,10 @@ _KERNEL_SIGS = {
     "psx_q8_encode": (i32, [vp, i32, vp, i64, vp, i64, i64, vp]),
     "psx_q8_apply_multi": (i32, [vp, vp, i32, vp, i64, i64, i64, f32, f32, f32, f32, i32, vp, vp]),
     "psx_q8_decode": (i32, [vp, vp, i64, i64, i64, f32, i32, vp]),
+    "psx_sign1_payload_bytes": (i64, [i64]),
+    "psx_sign1_encode": (i32, [vp, i32, vp, i64, vp, i64, i64, vp]),
+    "psx_sign1_apply_multi": (i32, [vp, vp, i32, vp, i64, i64, i64, f32, f32, f32, f32, i32, vp, vp]),
+    "psx_sign1_decode": (i32, [vp, vp, i64, i64, i64, f32, i32, vp]),
     "psx_lars_table_size": (i32, []),
     "psx_lars_chunk": (i32, []),
     "psx_lars_apply_multi": (i32, [vp, vp, i32, i32, vp, vp, i64, vp, i32, i32, vp, vp, f32, f32, f32, f32, f32, f32,

@@ -655,6 +655,64 @@ def q8_decode(payload, dst, n=None, scale=1.0, add=False, off=0, cnt=None):
           "q8_decode")
 
 
+def sign1_payload_bytes(n: int) -> int:
+    return kernels().psx_sign1_payload_bytes(int(n))
+
+
+def _sign1_range(n, off, cnt):
+    cnt = n - off if cnt is None else cnt
+    assert off % 256 == 0 and 0 <= off and off + cnt <= n and ((off + cnt) % 256 == 0 or off + cnt == n), \
+        "sign1 sub-range: 256-aligned start, end on a block or at n"
+    return int(off), int(cnt)
+
+
+def _sign1_payload_ok(payload, n) -> bool:
+    return payload.dtype == torch.uint8 and payload.is_contiguous() and payload.numel() == sign1_payload_bytes(n)
+
+
+def sign1_encode(g, resid, payload, n=None, off=0, cnt=None):
+    """Error-feedback 1-bit sign encode of (resid + g)[off:off+cnt] into ``payload`` (the whole
+    arena's sign1 payload, parallel/sign1.py); resid keeps acc - deq (csrc/kernels/sign1.hip).
+    g: fp32 or fp16, >= n elements; resid: fp32, >= n elements."""
+    n = resid.numel() if n is None else n
+    off, cnt = _sign1_range(n, off, cnt)
+    assert g.dtype in (torch.float16, torch.float32) and g.numel() >= n and g.device == resid.device, "sign1_encode g"
+    assert resid.dtype == torch.float32 and resid.numel() >= n, "sign1_encode resid"
+    assert _sign1_payload_ok(payload, n) and payload.device == resid.device, "sign1_encode payload"
+    check(kernels().psx_sign1_encode(ptr(g), int(g.dtype == torch.float16), ptr(resid), n, ptr(payload), off, cnt,
+                                     stream_ptr()), "sign1_encode")
+
+
+def sign1_apply_multi(p, payloads, lr, gscale=1.0, momentum=0.0, wd=0.0, buf=None, first=False, n=None, img=None,
+                      off=0, cnt=None):
+    """p[off:off+cnt] -= lr*(gscale * sum_k deq(payloads[k]) + wd*p) [momentum]: the server update
+    straight from the gathered sign1 payloads, decoded and summed in fp32 in list order (same
+    update tail as sgd_apply_multi). At most 32 payloads; one payload is the async / W = 1 apply."""
+    n = p.numel() if n is None else n
+    off, cnt = _sign1_range(n, off, cnt)
+    assert 1 <= len(payloads) <= 32
+    assert p.dtype == torch.float32 and p.numel() >= n, "sign1_apply_multi p"
+    assert all(_sign1_payload_ok(s, n) and s.device == p.device for s in payloads), "sign1_apply_multi"
+    if buf is not None:
+        assert buf.dtype == torch.float32 and buf.numel() >= n and buf.device == p.device, "sign1_apply_multi buf"
+    if img is not None:
+        assert img.dtype == torch.bfloat16 and img.numel() >= n and img.device == p.device, "sign1_apply_multi img"
+    arr = (C.c_void_p * len(payloads))(*[s.data_ptr() for s in payloads])
+    check(kernels().psx_sign1_apply_multi(ptr(p), arr, len(payloads), ptr(buf), n, off, cnt, float(lr),
+                                          float(gscale), float(momentum), float(wd), int(first), ptr(img),
+                                          stream_ptr()), "sign1_apply_multi")
+
+
+def sign1_decode(payload, dst, n=None, scale=1.0, add=False, off=0, cnt=None):
+    """dst[off:off+cnt] = [dst +] scale * deq(payload) (fp32 dst of >= n elements)."""
+    n = dst.numel() if n is None else n
+    off, cnt = _sign1_range(n, off, cnt)
+    assert dst.dtype == torch.float32 and dst.numel() >= n, "sign1_decode dst"
+    assert _sign1_payload_ok(payload, n) and payload.device == dst.device, "sign1_decode payload"
+    check(kernels().psx_sign1_decode(ptr(payload), ptr(dst), n, off, cnt, float(scale), int(add), stream_ptr()),
+          "sign1_decode")
+
+
 def _wire_srcs(srcs, n, dev, state, what):
     """The checked host array of a round's gathered wires: 1..32 sources (kMaxSrc,
     csrc/kernels/wire.hpp) of one dtype, fp16 or fp32, >= n elements each, on ``dev``, contiguous,

@@ -102,6 +102,7 @@ class Rule:
     """The parts of a rule that have a default (the module docstring lists them all)."""
     whole, adam, table, refusal = False, False, False, ""
     device_q8 = None  # the device form that decodes q8 payloads inside the update, where there is one
+    device_sign1 = None  # the same for sign1 payloads
 
     def scatters(self, cfg) -> bool:
         return False
@@ -111,9 +112,9 @@ class Rule:
 
 
 class SGD(Rule):
-    """p <- p - lr * (weight * g [+ wd p]) [momentum]: csrc/kernels/optim.hip (q8 payloads:
-    csrc/kernels/q8.hip, decoded inside the update). Element-wise: any range is legal, and the
-    ranges of one round share the momentum 'first step' flag."""
+    """p <- p - lr * (weight * g [+ wd p]) [momentum]: csrc/kernels/optim.hip (q8 / sign1
+    payloads: csrc/kernels/q8.hip / sign1.hip, decoded inside the update). Element-wise: any range
+    is legal, and the ranges of one round share the momentum 'first step' flag."""
 
     def scatters(self, cfg) -> bool:
         return not cfg.momentum and not cfg.weight_decay  # no optimizer state to keep in step
@@ -131,6 +132,9 @@ class SGD(Rule):
 
     def device_q8(self, s, payloads, weight, img):
         K.q8_apply_multi(s.params, payloads, s.lr, **self._kw(s, weight, 0, s.n, img))
+
+    def device_sign1(self, s, payloads, weight, img):
+        K.sign1_apply_multi(s.params, payloads, s.lr, **self._kw(s, weight, 0, s.n, img))
 
     def host(self, s, srcs, weight, lo, hi, summed):
         p = s.params[lo:hi]
@@ -160,7 +164,7 @@ class Guard(SGD):
     whole = True
     refusal = ("--clip-norm / --skip-nonfinite need the whole gradient's norm before the first parameter moves: a "
                "partial range [{lo}, {hi}) of {n} cannot be applied (no bucketed or sharded updates)")
-    device_q8, scatters = None, Rule.scatters
+    device_q8, device_sign1, scatters = None, None, Rule.scatters
 
     def device(self, s, srcs, weight, lo, hi, img, summed):
         stage(s, srcs, "guard", s._guard_state, lr=s.lr, clip_norm=s.cfg.clip_norm, **self._kw(s, weight, lo, hi, img))
@@ -196,7 +200,7 @@ class LARS(SGD):
     whole = table = True
     refusal = ("--optimizer lars needs every tensor's norm before its first element moves: a partial range "
                "[{lo}, {hi}) of {n} cannot be applied (no bucketed or sharded updates)")
-    device_q8, scatters = None, Rule.scatters
+    device_q8, device_sign1, scatters = None, None, Rule.scatters
 
     def device(self, s, srcs, weight, lo, hi, img, summed):
         s._ratios_applied = True

@@ -54,7 +54,7 @@ def _device_for(local_rank: int):
 
 def _wire_dtype(cfg):
     """Dtype of the worker's dense gradient buffer: fp16 wire (reference cast), fp32 for the
-    uncompressed wire and as the top-k / q8 codecs' input (their residual is fp32)."""
+    uncompressed wire and as the top-k / q8 / sign1 codecs' input (their residual is fp32)."""
     return torch.float16 if cfg.codec == "fp16" else torch.float32
 
 
@@ -682,10 +682,11 @@ def _server_rounds(cfg, server, chan, steps, device, skip, t, ctx):
         from .topk import empty_payload
 
         zeros = empty_payload(server.n, cfg.topk_ratio, device)  # contributes no entries to the gather
-    elif cfg.codec == "q8":
-        from .q8 import empty_payload
+    elif cfg.codec in ("q8", "sign1"):
+        from . import q8, sign1
 
-        zeros = empty_payload(server.n, device)  # rank 0's slot in the gather; the channel drops it
+        # rank 0's slot in the gather; the channel drops it
+        zeros = (q8 if cfg.codec == "q8" else sign1).empty_payload(server.n, device)
     else:
         zeros = torch.zeros(server.n, dtype=_wire_dtype(cfg), device=device)
     zbuf = torch.zeros(server.layout.buffer_numel, dtype=torch.float32, device=device) if cfg.bn_sync else None

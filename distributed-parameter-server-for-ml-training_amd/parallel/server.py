@@ -29,7 +29,7 @@ from ..utils import metrics as M
 from ..ops import kernels as K
 from ..utils import trace
 from . import control as CP
-from . import q8, topk
+from . import q8, sign1, topk
 from . import rules as R
 from .core import APPLY, WAIT, ServerCore
 
@@ -44,7 +44,7 @@ def arena_sha256(arena: torch.Tensor) -> str:
 
 
 def _wire_bytes(grads: torch.Tensor, n: int) -> int:
-    """Bytes one push moves: a q8 payload whole, otherwise the first n elements of the buffer."""
+    """Bytes one push moves: a q8 / sign1 payload whole, otherwise the first n elements of the buffer."""
     if grads.dtype == torch.uint8:
         return grads.numel()
     return min(n, grads.numel()) * grads.element_size()
@@ -131,7 +131,7 @@ class ParameterServer:
     # ------------------------------------------------------------------ numerics
     def apply(self, grads: torch.Tensor, weight: float, worker_id: int | None = None):
         """p <- p - lr * (weight * g [+ wd p]) [momentum]; grads are fp16 wire, fp32, or a top-k
-        (int32) / q8 (uint8) payload. ``worker_id``: the pushing worker of an async push (delay
+        (int32) / q8 or sign1 (uint8) payload. ``worker_id``: the pushing worker of an async push (delay
         compensation reads its backup)."""
         trace.mark("psx.apply")
         t0 = self._time_begin()
@@ -145,15 +145,29 @@ class ParameterServer:
                 self._wire_stale = True  # the bf16 image was not written by this update
                 return self.finish_round_apply(self._time_end(t0))
             grads = self._dense_of(grads)
-        if grads.dtype == torch.uint8:  # q8 payload (parallel/q8.py): decoded inside the update
-            self._apply_q8([grads], weight)
+        if grads.dtype == torch.uint8:  # q8 / sign1 payload: decoded inside the update
+            self._apply_payloads([grads], weight)
         else:
             self.apply_range(grads[: self.n], weight, 0, self.n)
         return self.finish_round_apply(self._time_end(t0))
 
-    def _apply_q8(self, payloads: list, weight: float):
-        """The update from q8 payloads, decoded and summed in fp32 in list order (update_range)."""
+    def _apply_payloads(self, payloads: list, weight: float):
+        """The update from q8 or sign1 payloads (one codec per list), decoded and summed in fp32 in
+        list order (update_range)."""
         self.update_range(payloads, weight, 0, self.n)
+
+    _apply_q8 = _apply_payloads  # the name from before sign1 shared the route
+
+    def _payload_codec(self, payload: torch.Tensor):
+        """The codec module (q8 or sign1) of a uint8 payload, told on the host by its byte length
+        — the configured codec's first, where an arena of a few elements gives both the same —
+        never by reading the device header back."""
+        own = {"q8": q8, "sign1": sign1}.get(self.cfg.codec)
+        for m in ((own,) if own is not None else ()) + (q8, sign1):
+            if payload.numel() == m.payload_bytes(self.n):
+                return m
+        raise ValueError(f"a uint8 push of {payload.numel()} bytes is neither a q8 nor a sign1 payload of "
+                         f"{self.n} parameters")
 
     # ------------------------------------------------------------------ the one update entry
     _IMG_OF_WIRE = object()
@@ -163,7 +177,7 @@ class ParameterServer:
         here. ``srcs``: fp16 / fp32 wires that each hold the gradient of exactly that range in their
         first hi - lo elements, summed in fp32 in list order, or the aggregation buffer itself (a
         decoded or accumulated sum); ``summed``: the one source already is the round's sum, taken
-        as is. q8 payloads (whole range): decoded inside the kernel by a rule that has such a
+        as is. q8 / sign1 payloads (whole range): decoded inside the kernel by a rule that has such a
         device form, otherwise into the aggregation buffer first. A rule that needs the whole arena
         refuses a partial range. ``img``: the bf16 image slice that receives the updated range, on
         the device in the same pass (default: the weight wire's, which an ``img`` of the caller's,
@@ -178,8 +192,9 @@ class ParameterServer:
         if on_device and not own_img:
             img = self.wire.img[lo:hi] if self.wire is not None else None
         if srcs[0].dtype == torch.uint8:
-            if on_device and rule.device_q8 is not None:
-                return rule.device_q8(self, srcs, weight, img)
+            in_kernel = rule.device_sign1 if self._payload_codec(srcs[0]) is sign1 else rule.device_q8
+            if on_device and in_kernel is not None:
+                return in_kernel(self, srcs, weight, img)
             for i, p in enumerate(srcs):
                 self._dense_of(p, add=i > 0)
             srcs, summed = [self.agg], True
@@ -221,7 +236,7 @@ class ParameterServer:
     def _apply_dc(self, grads: torch.Tensor, weight: float, worker_id):
         """The delay-compensated update of one async push: g~ = g + lam * g * g * (w - bak), lam =
         dc_lambda or dc_lambda / sqrt(ms + dc_eps) (adaptive; ms = decay * ms + (1 - decay) * g * g
-        on every apply), then the usual tail. q8 / top-k payloads are decoded into the aggregation
+        on every apply), then the usual tail. q8 / sign1 / top-k payloads are decoded into the aggregation
         buffer first. A worker without a valid backup (no fetch yet, or after a resume) is applied
         uncompensated and counted. Device: one launch of csrc/kernels/dcasgd.hip; CPU arena: the
         same formula in torch (equal to a tolerance, not bit for bit)."""
@@ -299,11 +314,11 @@ class ParameterServer:
         return topk.topk_k(self.n, self.cfg.topk_ratio)
 
     def _dense_of(self, payload: torch.Tensor, out: torch.Tensor | None = None, add: bool = False):
-        """Top-k / q8 payload -> dense fp32 gradient (into the aggregation buffer by default)."""
+        """Top-k / q8 / sign1 payload -> dense fp32 gradient (into the aggregation buffer by default)."""
         if out is None:
             out = self._agg()
         if payload.dtype == torch.uint8:
-            return q8.decode(payload, self.n, out=out, add=add)
+            return self._payload_codec(payload).decode(payload, self.n, out=out, add=add)
         if not add:
             out.zero_()
         return topk.decode_add(payload, out, 1.0, self._kcap)
@@ -445,7 +460,7 @@ class ParameterServer:
                 if grads.dtype == torch.int32:  # decoded into the dense buffer first, as apply_gathered
                     self._dense_of(grads)
                     self.apply(self.agg, res.weight)
-                elif grads.dtype == torch.uint8:  # one-source q8_apply_multi, as apply_q8_sources
+                elif grads.dtype == torch.uint8:  # one-source payload apply, as apply_payload_sources
                     self.apply(grads, res.weight)
                 else:
                     trace.mark("psx.apply")
@@ -564,11 +579,12 @@ class ParameterServer:
             return True
         return False
 
-    def apply_q8_sources(self, payloads: list, members: list[int], local_steps: list[int],
-                         buffers_sum: torch.Tensor | None = None) -> bool:
-        """Sync round whose W q8 payloads were gathered to rank 0 (one per contributing worker):
-        the bookkeeping of apply_sources, then one launch that decodes and sums them in fp32 in
-        list order inside the update (kernels.q8_apply_multi) — no dense staging buffer."""
+    def apply_payload_sources(self, payloads: list, members: list[int], local_steps: list[int],
+                              buffers_sum: torch.Tensor | None = None) -> bool:
+        """Sync round whose W q8 or sign1 payloads were gathered to rank 0 (one per contributing
+        worker): the bookkeeping of apply_sources, then one launch that decodes and sums them in
+        fp32 in list order inside the update (kernels.q8_apply_multi / sign1_apply_multi) — no dense
+        staging buffer."""
         res = None
         for wid, ls in zip(members, local_steps):
             res = self.core.on_push(wid, ls)
@@ -577,11 +593,13 @@ class ParameterServer:
             return False
         trace.mark("psx.apply")
         t0 = self._time_begin()
-        self._apply_q8(list(payloads), res.weight)
+        self._apply_payloads(list(payloads), res.weight)
         self.finish_round_apply(self._time_end(t0))
         if buffers_sum is not None:
             self.set_buffers_from_sum(buffers_sum, len(members))
         return True
+
+    apply_q8_sources = apply_payload_sources  # the name from before sign1 shared the route
 
     # ------------------------------------------------------------------ checkpoint
     def checkpoint(self, path: str | None = None) -> str:
@@ -678,8 +696,9 @@ class ParameterServer:
         if self.cfg.codec == "topk":
             words = topk.payload_words(self._kcap)
             slots = {w: torch.empty(words, dtype=torch.int32, device=self.device) for w in rank_of}
-        elif self.cfg.codec == "q8":
-            slots = {w: torch.empty(q8.payload_bytes(n), dtype=torch.uint8, device=self.device) for w in rank_of}
+        elif self.cfg.codec in ("q8", "sign1"):
+            nbytes = (q8 if self.cfg.codec == "q8" else sign1).payload_bytes(n)
+            slots = {w: torch.empty(nbytes, dtype=torch.uint8, device=self.device) for w in rank_of}
         else:
             wire_dtype = torch.float16 if self.cfg.codec == "fp16" else torch.float32
             slots = {w: torch.empty(n, dtype=wire_dtype, device=self.device) for w in rank_of}

@@ -88,8 +88,8 @@ class InProcessChannel:
 class SyncCollectiveChannel(WatchedRounds):
     """All ranks call push/fetch in lockstep. Rank 0 may or may not train (topology).
 
-    Push (top-k / q8 payloads): gathered to rank 0 and decoded there (ParameterServer.apply_gathered /
-    apply_q8_sources).
+    Push (top-k / q8 / sign1 payloads): gathered to rank 0 and decoded there
+    (ParameterServer.apply_gathered / apply_payload_sources).
     Push (dense wire): the workers' wires are gathered to rank 0 and summed there in fp32 by the
     update kernel, in a fixed worker order — the reference's decode-to-fp32 + average
     (server.py:145-169,232-237), deterministic, and every worker's transfer on its own link.
@@ -175,7 +175,7 @@ class SyncCollectiveChannel(WatchedRounds):
 
     def _push(self, worker_id, grads, local_step, buffers=None):
         sparse = grads.dtype == torch.int32  # top-k payloads cannot be summed by a reduce: gather
-        q8w = grads.dtype == torch.uint8     # nor can q8 payloads (a scale per block and source)
+        q8w = grads.dtype == torch.uint8     # nor can q8 / sign1 payloads (a scale per block and source)
         world = getattr(self.t, "world_size", 1)
         dense_gather = not sparse and not q8w and self.agg_mode == "gather" and world > 1
         if sparse or q8w:
@@ -194,7 +194,7 @@ class SyncCollectiveChannel(WatchedRounds):
                 self.server.apply_gathered(gathered, self.members, steps, buffers_sum=buffers)
             elif q8w:  # a dedicated server's own slot is the empty payload: dropped here
                 srcs = gathered if self.root_worker else gathered[1:]
-                self.server.apply_q8_sources(srcs, self.members, steps, buffers_sum=buffers)
+                self.server.apply_payload_sources(srcs, self.members, steps, buffers_sum=buffers)
             elif dense_gather:
                 srcs = ([grads] if self.root_worker else []) + [self._gbufs[r] for r in sorted(self._gbufs)]
                 self.server.apply_sources(srcs, self.members, steps, buffers_sum=buffers)
@@ -296,7 +296,8 @@ class Worker:
         self.timer = M.PhaseTimer(device=getattr(compute, "device", None))
         self.sampler = None
         # the error-feedback encoder of the push codec (owns the residual and the payload buffer):
-        # top-k (parallel/topk.py) or block-scaled int8 (parallel/q8.py); None = dense wire
+        # top-k (parallel/topk.py), block-scaled int8 (parallel/q8.py) or 1-bit sign
+        # (parallel/sign1.py); None = dense wire
         self.encoder = None
         if cfg.codec == "topk":
             from .topk import TopKCodec
@@ -306,6 +307,10 @@ class Worker:
             from .q8 import Q8Codec
 
             self.encoder = Q8Codec(compute.layout.param_numel, getattr(compute, "device", "cpu"))
+        elif cfg.codec == "sign1":
+            from .sign1 import Sign1Codec
+
+            self.encoder = Sign1Codec(compute.layout.param_numel, getattr(compute, "device", "cpu"))
 
     # ---------------------------------------------------------------- reference API
     def connect_to_server(self):
@@ -359,7 +364,7 @@ class Worker:
         if self.cfg.bn_sync:
             bufs = self.compute.local_arena[self.compute.layout.param_numel:]
         g = self.compute.grads
-        if self.encoder is not None:  # --codec topk / q8: error-feedback payload
+        if self.encoder is not None:  # --codec topk / q8 / sign1: error-feedback payload
             if self.recover is not None and self.cfg.codec == "topk":  # sync shrink runs dense or top-k only
                 self._snapshot_resid()
             g = self.encoder.encode(g)

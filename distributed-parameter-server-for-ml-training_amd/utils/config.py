@@ -9,7 +9,8 @@ Keeps every flag and environment variable of the reference with the same default
   worker  --server (env PARAMETER_SERVER_ADDRESS, localhost:8000), --worker-name,
           --epochs 3, --batch-size 128, --lr 0.1, --sync-steps 1
 
-and adds the MI355X-native knobs: --gpus/--nproc, --codec, --topk-ratio,
+and adds the MI355X-native knobs: --gpus/--nproc, --codec {none,fp16,q8,sign1,topk},
+--topk-ratio,
 --dtype, --momentum/--weight-decay (server optimizer, default 0 = reference parity),
 --optimizer {sgd,lars,adamw,lamb} with --lars-trust/--lars-eps and --adam-beta1/--adam-beta2/--adam-eps,
 --warmup-steps (linear lr warmup of the server update),
@@ -53,7 +54,7 @@ class PSConfig:
     gpus: int = 1                  # processes / GPUs on this node (1 = server+worker co-located)
     topology: str = "colocated"    # colocated: rank 0 = PS + worker 0; dedicated: rank 0 = PS only;
     #                                sharded: every rank = worker + 1/world of the PS (parallel/sharded.py)
-    codec: str = "fp16"            # none (fp32 wire) | fp16 (reference) | q8 (block-scaled int8) | topk
+    codec: str = "fp16"            # none (fp32 wire) | fp16 (reference) | q8 (block-scaled int8) | sign1 (1 bit) | topk
     topk_ratio: float = 0.01
     # compute dtype of the HIP engine: fp32 = the reference's training precision (worker.py:333-348;
     # exact-f32 MFMA), bf16 = the fast path (bf16 operands, fp32 accumulation and master weights)
@@ -152,8 +153,8 @@ class PSConfig:
             raise ValueError("Number of workers must be between 1 and 32")
         if self.eval_workers not in ("all", "first"):
             raise ValueError("--eval-workers must be all or first")
-        if self.codec not in ("none", "fp16", "q8", "topk"):
-            raise ValueError(f"--codec must be none, fp16, q8 or topk, got {self.codec!r}")
+        if self.codec not in ("none", "fp16", "q8", "sign1", "topk"):
+            raise ValueError(f"--codec must be none, fp16, q8, sign1 or topk, got {self.codec!r}")
         if self.topology not in ("colocated", "dedicated", "sharded"):
             raise ValueError(f"--topology must be colocated, dedicated or sharded, got {self.topology!r}")
         if self.optimizer not in ("sgd", "lars", "adamw", "lamb"):
@@ -240,7 +241,7 @@ class PSConfig:
     def resolve_overlap(self, world: int) -> bool:
         """--overlap / --no-overlap, or auto: bucketed rounds when there are peers to exchange
         with and the round qualifies (sync, one push per batch, dense wire, rank-0 server). The
-        error-feedback codecs (q8, topk) encode the whole gradient at once, and a whole-arena update
+        error-feedback codecs (q8, sign1, topk) encode the whole gradient at once, and a whole-arena update
         (whole_arena_update) cannot start before the last bucket: no bucketed rounds. --optimizer
         adamw is element-wise and stays eligible."""
         if self.overlap is None:
@@ -289,7 +290,10 @@ def add_arguments(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
     A("--num-classes", type=int, default=None)
     A("--gpus", "--nproc", dest="gpus", type=int, default=None)
     A("--topology", choices=["colocated", "dedicated", "sharded"], default=None)
-    A("--codec", choices=["none", "fp16", "q8", "topk"], default=None)
+    A("--codec", choices=["none", "fp16", "q8", "sign1", "topk"], default=None,
+      help="gradient wire: fp16 cast (reference, default), none (fp32), q8 (block-scaled int8, 1.016 B/param), "
+           "sign1 (1-bit sign + a scale per 256, 0.1406 B/param) or topk; q8, sign1 and topk keep an error-feedback "
+           "residual on the worker")
     A("--topk-ratio", type=float, default=None)
     A("--dtype", choices=["fp32", "bf16"], default=None,
       help="worker compute precision: fp32 (reference, default) or bf16 (fast path)")

@@ -13,6 +13,8 @@
 * ``psx_fp32_q8``     the same with the block-scaled int8 wire and error feedback (--codec q8); also
                       compared against ``psx_fp32`` (``q8_vs_psx_fp32`` in the JSON), next to the
                       torch seed-to-seed spread.
+* ``psx_fp32_sign1``  the same with the 1-bit sign wire and error feedback (--codec sign1); compared
+                      against ``psx_fp32`` in the same way (``sign1_vs_psx_fp32``).
 * ``psx_fp32_lars``   psx_fp32 with the layer-wise adaptive server optimizer (--optimizer lars, momentum
                       0.9, weight decay 5e-4, trust 0.001, lr ``--lars-lr``, default 2.0: the
                       trust ratio scales every tensor's step to lr * 0.001 * |w| / |g|, so its lr is
@@ -227,6 +229,7 @@ def main():
                      ("psx_fp32", lambda: run_psx(args, train, test, "fp32", "fp16")),
                      ("psx_fp32_wire32", lambda: run_psx(args, train, test, "fp32", "none")),
                      ("psx_fp32_q8", lambda: run_psx(args, train, test, "fp32", "q8")),
+                     ("psx_fp32_sign1", lambda: run_psx(args, train, test, "fp32", "sign1")),
                      ("psx_fp32_lars", lambda: run_psx(args, train, test, "fp32", "fp16", **lars)),
                      ("psx_fp32_adamw", lambda: run_psx(args, train, test, "fp32", "fp16", **adamw)),
                      ("psx_fp32_lamb", lambda: run_psx(args, train, test, "fp32", "fp16", **lamb)),
@@ -251,7 +254,8 @@ def main():
                      "test_acc_diff_pp": r["test_acc"] - runs["torch_fp32"]["test_acc"]}
         print(f"  vs torch_fp32: {name:18s} {json.dumps(cmp[name])}", flush=True)
     vs_psx = {}
-    for name in ("psx_fp32_q8", "psx_fp32_lars", "psx_fp32_adamw", "psx_fp32_lamb", "psx_fp32_lars_warmup"):
+    for name in ("psx_fp32_q8", "psx_fp32_sign1", "psx_fp32_lars", "psx_fp32_adamw", "psx_fp32_lamb",
+                 "psx_fp32_lars_warmup"):
         if name not in runs or "psx_fp32" not in runs:
             continue
         d = smooth(runs[name]["loss"], args.window) - smooth(runs["psx_fp32"]["loss"], args.window)
@@ -270,6 +274,7 @@ def main():
     out = {"config": vars(args), "data": "synthetic_hard: 4x4 class prototypes (std 12) + pixel noise (std 64), "
                                           "20% label noise, 100 classes",
            "runs": runs, "vs_torch_fp32": cmp, "q8_vs_psx_fp32": vs_psx.get("psx_fp32_q8"),
+           "sign1_vs_psx_fp32": vs_psx.get("psx_fp32_sign1"),
            "lars_vs_psx_fp32": vs_psx.get("psx_fp32_lars"), "adamw_vs_psx_fp32": vs_psx.get("psx_fp32_adamw"),
            "lamb_vs_psx_fp32": vs_psx.get("psx_fp32_lamb"),
            "lars_warmup_vs_psx_fp32": vs_psx.get("psx_fp32_lars_warmup"),
