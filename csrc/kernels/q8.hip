@@ -20,6 +20,9 @@
 //
 //   * q8_encode      : one streaming pass, a wave owns a block (64 lanes x 4 elements; 16-byte
 //                      loads of g and resid, wave-level shuffle reduction, no LDS, no barrier)
+//   * fetchq8_encode : the same pass for the fetch wire (--fetch-codec q8delta): the block is
+//                      d = arena - shadow and the server's shadow of the workers' copy becomes
+//                      shadow + deq, what q8_decode(add) leaves on every worker
 //   * q8_apply_multi : the server update straight from the gathered payloads, 16 int8 per lane
 //                      per source (4 rows of a wave's 1024 elements), same update tail as
 //                      sgd_apply_multi (sgd_tail.hpp)
@@ -68,6 +71,33 @@ PSX_DEV void ld_g4(const uint16_t* g, long i, float (&v)[4]) {
 // int8 number j (0..3) of a packed word, as float
 PSX_DEV float q8_f(uint32_t w, int j) { return (float)((int)(w << (24 - 8 * j)) >> 24); }
 
+// A wave quantises one block: lane l holds elements 4 l .. 4 l + 3 of it in v. Gives the block's
+// scale (wave-uniform), the lane's four int8 packed into w and their dequantised values
+// deq[j] = float(q_j) * scale, by the arithmetic in the header.
+PSX_DEV void q8_quant4(const float (&v)[4], float& scale, uint32_t& w, float (&deq)[4]) {
+  float amax = 0.f;
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float a = fabsf(v[j]);
+    bad = bad || !(a <= FLT_MAX);  // NaN or Inf (fmaxf below drops NaNs)
+    amax = fmaxf(amax, a);
+  }
+  amax = wave_max(amax);
+  const bool blk_bad = __ballot(bad) != 0ull;
+  scale = blk_bad ? __builtin_nanf("") : amax / 127.0f;
+  const float inv = (!blk_bad && amax > 0.f) ? 127.0f / amax : 0.f;
+  w = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float r = rintf(v[j] * inv);
+    r = r == r ? r : 0.f;
+    r = fminf(fmaxf(r, -127.f), 127.f);
+    deq[j] = r * scale;  // r is float(q) exactly
+    w |= ((uint32_t)(int)r & 0xffu) << (8 * j);
+  }
+}
+
 // Blocks [blk0, blk1) of the arena. VEC: g, resid 16-byte (fp16 g: 8-byte) aligned; the tail
 // block (the one holding element n - 1 when n % 256 != 0) and the unaligned form go element by
 // element and touch nothing at or past n in g or resid. q words past n within the padded section
@@ -97,35 +127,68 @@ __global__ __launch_bounds__(256) void q8_encode_kernel(const GT* __restrict__ g
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[j] = e + j < n ? resid[e + j] + ld_g1(g, e + j) : 0.f;
     }
-    float amax = 0.f;
-    bool bad = false;
+    uint32_t w;
+    float scale, deq[4], res[4];
+    q8_quant4(acc, scale, w, deq);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float a = fabsf(acc[j]);
-      bad = bad || !(a <= FLT_MAX);  // NaN or Inf (fmaxf below drops NaNs)
-      amax = fmaxf(amax, a);
-    }
-    amax = wave_max(amax);
-    const bool blk_bad = __ballot(bad) != 0ull;
-    const float scale = blk_bad ? __builtin_nanf("") : amax / 127.0f;
-    const float inv = (!blk_bad && amax > 0.f) ? 127.0f / amax : 0.f;
-    uint32_t w = 0;
-    float res[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float r = rintf(acc[j] * inv);
-      r = r == r ? r : 0.f;
-      r = fminf(fmaxf(r, -127.f), 127.f);
-      const float deq = r * scale;  // r is float(q) exactly
-      res[j] = acc[j] - deq;
-      w |= ((uint32_t)(int)r & 0xffu) << (8 * j);
-    }
+    for (int j = 0; j < 4; ++j) res[j] = acc[j] - deq[j];
     if (VEC && full) {
       *reinterpret_cast<f32x4*>(resid + e) = (f32x4){res[0], res[1], res[2], res[3]};
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (e + j < n) resid[e + j] = res[j];
+    }
+    if ((e >> 2) < qwords) qw[e >> 2] = w;
+    if (lane == 0) scales[b] = scale;
+  }
+}
+
+// The fetch wire's encode (--fetch-codec q8delta, parallel/fetchq8.py): the same pass with
+// d = arena - shadow in place of resid + g, and shadow = shadow + deq (the copy every worker
+// holds) in place of the residual. Same forms, same bounds: nothing at or past n is touched in
+// arena or shadow. 13 bytes per element: 8 read, 4 + 1 written.
+template <bool VEC>
+__global__ __launch_bounds__(256) void fetchq8_encode_kernel(const float* __restrict__ arena,
+                                                             float* __restrict__ shadow, long n, long blk0, long blk1,
+                                                             float* __restrict__ scales, uint32_t* __restrict__ qw,
+                                                             long qwords, int* __restrict__ hdr) {
+  const int lane = threadIdx.x & 63;
+  if (hdr != nullptr && blockIdx.x == 0 && threadIdx.x < 4) {
+    const long nblk = (n + kQ8Block - 1) / kQ8Block;
+    hdr[threadIdx.x] = threadIdx.x == 0 ? kQ8Magic : threadIdx.x == 1 ? (int)n : threadIdx.x == 2 ? kQ8Block : (int)nblk;
+  }
+  const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
+  for (long b = blk0 + wave; b < blk1; b += nwaves) {
+    const long e = b * kQ8Block + lane * 4;
+    const bool full = (b + 1) * kQ8Block <= n;  // wave-uniform
+    float sh[4], d[4];
+    if (VEC && full) {
+      const f32x4 a = *reinterpret_cast<const f32x4*>(arena + e);
+      const f32x4 s = *reinterpret_cast<const f32x4*>(shadow + e);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        sh[j] = s[j];
+        d[j] = a[j] - s[j];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        sh[j] = e + j < n ? shadow[e + j] : 0.f;
+        d[j] = e + j < n ? arena[e + j] - sh[j] : 0.f;
+      }
+    }
+    uint32_t w;
+    float scale, deq[4];
+    q8_quant4(d, scale, w, deq);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sh[j] = sh[j] + deq[j];
+    if (VEC && full) {
+      *reinterpret_cast<f32x4*>(shadow + e) = (f32x4){sh[0], sh[1], sh[2], sh[3]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (e + j < n) shadow[e + j] = sh[j];
     }
     if ((e >> 2) < qwords) qw[e >> 2] = w;
     if (lane == 0) scales[b] = scale;
@@ -319,6 +382,30 @@ int psx_q8_encode(const void* g, int g_fp16, float* resid, long n, void* payload
   else if (vec) PSX_Q8E(float, true);
   else PSX_Q8E(float, false);
 #undef PSX_Q8E
+  return (int)hipGetLastError();
+}
+
+// Encode elements [off, off + cnt) of d = arena - shadow into `payload` (the whole arena's payload,
+// 16-byte aligned) and leave shadow = shadow + deq. arena, shadow: element 0 of the n-element fp32
+// arrays. The header is written by the call that covers block 0.
+int psx_fetchq8_encode(const float* arena, float* shadow, long n, void* payload, long off, long cnt,
+                       hipStream_t st) {
+  if (!q8_range_ok(n, off, cnt) || (uintptr_t)payload % 16 != 0) return (int)hipErrorInvalidValue;
+  if (cnt == 0) return 0;
+  const Q8Layout l = q8_layout(n);
+  uint8_t* pl = (uint8_t*)payload;
+  float* scales = (float*)(pl + l.scales_off);
+  uint32_t* qw = (uint32_t*)(pl + l.q_off);
+  const long qwords = (l.bytes - l.q_off) / 4;
+  const long blk0 = off / kQ8Block, blk1 = (off + cnt + kQ8Block - 1) / kQ8Block;
+  int* hdr = off == 0 ? (int*)pl : nullptr;
+  const dim3 grid(stream_grid((blk1 - blk0) * 64));
+  if ((uintptr_t)arena % 16 == 0 && (uintptr_t)shadow % 16 == 0)
+    hipLaunchKernelGGL(fetchq8_encode_kernel<true>, grid, dim3(256), 0, st, arena, shadow, n, blk0, blk1, scales, qw,
+                       qwords, hdr);
+  else
+    hipLaunchKernelGGL(fetchq8_encode_kernel<false>, grid, dim3(256), 0, st, arena, shadow, n, blk0, blk1, scales, qw,
+                       qwords, hdr);
   return (int)hipGetLastError();
 }
 

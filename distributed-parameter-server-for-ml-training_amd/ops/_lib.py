@@ -104,6 +104,7 @@ _KERNEL_SIGS = {
     "psx_topk_decode_add": (i32, [vp, vp, f32, i32, vp]),
     "psx_q8_payload_bytes": (i64, [i64]),
     "psx_q8_encode": (i32, [vp, i32, vp, i64, vp, i64, i64, vp]),
+    "psx_fetchq8_encode": (i32, [vp, vp, i64, vp, i64, i64, vp]),
     "psx_q8_apply_multi": (i32, [vp, vp, i32, vp, i64, i64, i64, f32, f32, f32, f32, i32, vp, vp]),
     "psx_q8_decode": (i32, [vp, vp, i64, i64, i64, f32, i32, vp]),
     "psx_sign1_payload_bytes": (i64, [i64]),

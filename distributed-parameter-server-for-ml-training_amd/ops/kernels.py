@@ -625,6 +625,21 @@ def q8_encode(g, resid, payload, n=None, off=0, cnt=None):
                                   stream_ptr()), "q8_encode")
 
 
+def fetchq8_encode(arena, shadow, payload, n=None, off=0, cnt=None):
+    """Delta encode of the fetch wire (--fetch-codec q8delta, parallel/fetchq8.py): the block-scaled
+    int8 of (arena - shadow)[off:off+cnt] into ``payload`` (the whole arena's q8 payload); shadow
+    becomes shadow + deq, what q8_decode(add=True) leaves on a worker (csrc/kernels/q8.hip).
+    arena, shadow: fp32, >= n elements."""
+    n = shadow.numel() if n is None else n
+    off, cnt = _q8_range(n, off, cnt)
+    assert arena.dtype == torch.float32 and arena.numel() >= n and arena.device == shadow.device, \
+        "fetchq8_encode arena"
+    assert shadow.dtype == torch.float32 and shadow.numel() >= n, "fetchq8_encode shadow"
+    assert _q8_payload_ok(payload, n) and payload.device == shadow.device, "fetchq8_encode payload"
+    check(kernels().psx_fetchq8_encode(ptr(arena), ptr(shadow), n, ptr(payload), off, cnt, stream_ptr()),
+          "fetchq8_encode")
+
+
 def q8_apply_multi(p, payloads, lr, gscale=1.0, momentum=0.0, wd=0.0, buf=None, first=False, n=None, img=None, off=0,
                    cnt=None):
     """p[off:off+cnt] -= lr*(gscale * sum_k deq(payloads[k]) + wd*p) [momentum]: the server update

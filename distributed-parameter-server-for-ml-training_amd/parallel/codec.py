@@ -1,7 +1,7 @@
 """Wire codecs of the PS protocol.
 
 Fetch (server -> worker). The reference ships the full fp32 state_dict on every fetch
-(reference: src/parameter_server/server.py:221-223, 44.9 MB for ResNet-18). Two fetch codecs:
+(reference: src/parameter_server/server.py:221-223, 44.9 MB for ResNet-18). Three fetch codecs:
 
 * ``fp32``     — the reference payload: the whole fp32 arena (params + BN buffers).
 * ``bf16conv`` — (default) exactly the bits a psx worker consumes: conv weights as bf16 (the HIP
@@ -9,6 +9,12 @@ Fetch (server -> worker). The reference ships the full fp32 state_dict on every 
   worker that receives fp32 and rounds locally computes bit-identical results) plus fp32 for
   every other tensor (BN affine, FC, BN running statistics). 22.5 MB instead of 44.9 MB per
   fetch for ResNet-18, and the worker-side arena is reconstructed exactly (bf16 -> fp32 is exact).
+* ``q8delta``  — the block-scaled int8 of what changed since the workers' copy, with error
+  feedback (parallel/fetchq8.py): 11.4 MB per fetch after one fp32 keyframe, either ``--dtype``.
+  Sync rounds on a rank-0 server and the loopback only: it is stateful (a shadow of the workers'
+  copy on the server), so ``FetchCodec`` only names it; ``ParameterServer.fetch_delta`` encodes and
+  ``fetchq8.Receiver`` applies. Rounds stay in Python and off the weight image: native_sync_enabled
+  and weight_image_enabled decline it by the conditions they already had.
 
 Push (worker -> server): the reference's fp16 cast (worker.py:264-268) is the default wire dtype
 of the gradient buffer; top-k sparsification lives in parallel/topk.py.
@@ -20,12 +26,17 @@ import torch
 
 class FetchCodec:
     def __init__(self, layout, kind: str = "bf16conv", device="cpu"):
-        if kind not in ("fp32", "bf16conv"):
+        if kind not in ("fp32", "bf16conv", "q8delta"):
             raise ValueError(f"unknown fetch codec {kind!r}")
         self.kind = kind
         self.layout = layout
         self.device = torch.device(device)
         n = layout.arena_numel
+        if kind == "q8delta":
+            # stateful (the server's shadow, a worker's Receiver): the sync channels drive it and own
+            # the buffers; this object names the wire and its size
+            self.wire = []
+            return
         if kind == "fp32":
             self.wire = [torch.zeros(n, dtype=torch.float32, device=self.device)]
             return
@@ -41,10 +52,17 @@ class FetchCodec:
 
     @property
     def nbytes(self) -> int:
+        if self.kind == "q8delta":
+            from .fetchq8 import payload_bytes
+
+            return payload_bytes(self.layout.arena_numel)
         return sum(t.numel() * t.element_size() for t in self.wire)
 
     def pack(self, arena: torch.Tensor):
         """server arena -> wire buffers (stream-ordered after the update)."""
+        if self.kind == "q8delta":
+            raise ValueError("the q8delta fetch wire encodes against the server's shadow "
+                             "(ParameterServer.fetch_delta), not from the arena alone")
         if self.kind == "fp32":
             self.wire[0].copy_(arena)
             return self.wire
@@ -54,6 +72,8 @@ class FetchCodec:
 
     def unpack(self, local_arena: torch.Tensor, wire=None):
         wire = wire if wire is not None else self.wire
+        if self.kind == "q8delta":
+            raise ValueError("the q8delta fetch wire adds to the state as last fetched (fetchq8.Receiver.apply)")
         if self.kind == "fp32":
             if wire[0].data_ptr() != local_arena.data_ptr():
                 local_arena.copy_(wire[0])

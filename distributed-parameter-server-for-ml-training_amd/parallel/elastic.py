@@ -55,7 +55,10 @@ def enabled(cfg, transport, world: int) -> bool:
             and cfg.codec in ("fp16", "none", "topk") and not cfg.bn_sync
             # _PyRollback snapshots the arena and the momentum buffer only: an AdamW or LAMB job takes
             # the restart-from-checkpoint path (the moments travel with the checkpoint)
-            and getattr(cfg, "optimizer", "sgd") not in ("adamw", "lamb"))
+            and getattr(cfg, "optimizer", "sgd") not in ("adamw", "lamb")
+            # after an aborted round the survivors may disagree on whether the fetch delta arrived, and
+            # the server's shadow of their copy is not in the rollback snapshots: the restart path
+            and getattr(cfg, "fetch_codec", "fp32") != "q8delta")
 
 
 def lost_error(e: BaseException) -> bool:

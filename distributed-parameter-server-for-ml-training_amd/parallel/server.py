@@ -29,7 +29,7 @@ from ..utils import metrics as M
 from ..ops import kernels as K
 from ..utils import trace
 from . import control as CP
-from . import q8, sign1, topk
+from . import fetchq8, q8, sign1, topk
 from . import rules as R
 from .core import APPLY, WAIT, ServerCore
 
@@ -102,6 +102,15 @@ class ParameterServer:
             self._dc_ms = torch.zeros(self.n, dtype=torch.float32, device=self.device)
         self.wire = None  # WeightWire fetch payload kept current by the apply (enable_weight_wire)
         self._wire_stale = False
+        # --fetch-codec q8delta (parallel/fetchq8.py): the fp32 shadow of what every worker holds and
+        # the payload of the last encode, both allocated at the first fetch (fetch_delta).
+        # shadow_valid goes false with every out-of-band change of the arena: the next fetch is a keyframe
+        self.fetch_q8 = getattr(cfg, "fetch_codec", "") == "q8delta"
+        self.shadow = self.fetch_payload = None
+        self.shadow_valid = False
+        self._fq_version = 0      # number of keyframes + encodes so far
+        self._fq_step = None      # the global step the shadow stands at
+        self._fq_key = False      # the last advance of the shadow was a keyframe
         self._pending = {}
         self.core = ServerCore(cfg.mode, self.total_workers, cfg.lr, cfg.staleness_bound, cfg.sync_semantics)
         self.start_time = time.time()
@@ -429,6 +438,33 @@ class ParameterServer:
         self.bytes_fetched += w.nbytes
         return w, gs
 
+    # ------------------------------------------------------------------ delta fetch (--fetch-codec q8delta)
+    def fetch_delta(self, keyframe: bool | None = None):
+        """Bring the shadow up to the current global step and return (version, keyframe, payload).
+        A keyframe sets shadow = arena (the caller ships the fp32 state; payload is not current);
+        otherwise one encode of arena - shadow advances the shadow by what ``payload`` decodes to
+        (fetchq8.encode_into). Once per update: further fetches of the same global step get the
+        same answer. ``keyframe``: what a lockstep round expects (every rank derives it from the
+        round number); None = decided here, by ``shadow_valid``."""
+        n = self.arena.numel()
+        if self.shadow is None:
+            self.shadow = torch.empty_like(self.arena)
+            self.fetch_payload = fetchq8.empty_payload(n, self.device)
+        gs = self.core.global_step
+        if keyframe is False and not self.shadow_valid:
+            raise RuntimeError("q8delta: the arena changed outside the updates in mid-job; the workers of a "
+                               "lockstep round cannot be told to take a keyframe")
+        if keyframe or not self.shadow_valid:
+            if not (self.shadow_valid and self._fq_key and self._fq_step == gs):
+                self.shadow.copy_(self.arena)
+                self._fq_version += 1
+            self.shadow_valid, self._fq_key, self._fq_step = True, True, gs
+        elif self._fq_step != gs:
+            fetchq8.encode_into(self.arena, self.shadow, self.fetch_payload, n)
+            self._fq_version += 1
+            self._fq_key, self._fq_step = False, gs
+        return self._fq_version, self._fq_key, self.fetch_payload
+
     def push_gradients(self, worker_id: int, grads: torch.Tensor, local_step: int, buffers=None) -> bool:
         """In-process push (single-process loopback runs). Sync: aggregate until the barrier
         completes, then apply the average. Async: staleness check + weighted apply.
@@ -625,6 +661,7 @@ class ParameterServer:
         arena, counters, step, mom, obj = ckpt.restore(path, self.layout)
         self.arena.copy_(arena.to(self.device))
         self._wire_stale = True
+        self.shadow_valid = False  # q8delta: the next fetch is a keyframe
         self.counters = counters
         self.core.global_step = step
         if mom is not None and self.momentum_buf is not None:
@@ -673,6 +710,8 @@ class ParameterServer:
         # and the sha256 of the fp32 arena bytes (bit-equality checks across runs / modes)
         m["final_param_checksum"] = float(self.arena.double().abs().sum())
         m["final_param_sha256"] = arena_sha256(self.arena)
+        if self.fetch_q8:  # what every worker holds (their local_arena_sha256); None: nothing was fetched
+            m["fetch_shadow_sha256"] = arena_sha256(self.shadow) if self.shadow_valid else None
         if extra:
             m.update(extra)
         if emit:

@@ -11,7 +11,8 @@ The protocol side is a *channel*:
 * ``InProcessChannel``  — direct calls into a ParameterServer object (1-process loopback; the
   server may host several simulated workers on one GPU);
 * ``SyncCollectiveChannel`` — sync mode over RCCL: push = reduce(sum) of the wire buffer to rank 0,
-  where the server applies the averaged update, fetch = broadcast of the arena (all ranks step
+  where the server applies the averaged update, fetch = broadcast of the arena, or with
+  ``--fetch-codec q8delta`` of the int8 delta against the workers' copy (all ranks step
   together, so the wait-for-N barrier is the collective itself);
 * ``AsyncChannel``      — async mode: control request on the shared-memory mailbox, bulk tensor by
   RCCL send/recv, reply (received flag, global step) on the worker's reply slot;
@@ -56,6 +57,12 @@ class InProcessChannel:
         self.server = server
         self.emit_on_last = emit_on_last
         self.image_wire = wire
+        # --fetch-codec q8delta: this simulated worker's end of the delta wire (parallel/fetchq8.py)
+        self.delta = None
+        if server.fetch_q8:
+            from .fetchq8 import Receiver
+
+            self.delta = Receiver(server.layout, server.device)
 
     def register(self, name, requested_id=-1):
         return self.server.register_worker(name, requested_id)
@@ -74,8 +81,29 @@ class InProcessChannel:
             if not shared:
                 self.image_wire.buf.copy_(src.buf)
             return gs
+        if self.delta is not None:
+            return self._fetch_delta(worker_id, local_arena)
         arena, gs = self.server.fetch_parameters(worker_id)
         local_arena.copy_(arena)
+        return gs
+
+    def _fetch_delta(self, worker_id, local_arena):
+        """--fetch-codec q8delta: a worker one encode behind the shadow adds the round's payload to
+        its own copy (the decode a remote worker runs); one that has had no keyframe yet, or is
+        further behind, takes the fp32 state (the shadow: the server's and the workers' bits)."""
+        s, d = self.server, self.delta
+        gs = s.note_fetch(worker_id)
+        version, key, payload = s.fetch_delta()
+        if d.version is not None and version == d.version + 1 and not key:
+            d.apply(local_arena, payload)
+            s.bytes_fetched += payload.numel()
+        elif version != d.version:
+            local_arena.copy_(s.shadow)
+            d.keyframe(local_arena)
+            s.bytes_fetched += 4 * s.shadow.numel()
+        else:  # nothing new since this worker's last fetch: only its own BN statistics go back
+            d.restore(local_arena)
+        d.version = version
         return gs
 
     def push(self, worker_id, grads, local_step, buffers=None):
@@ -141,9 +169,50 @@ class SyncCollectiveChannel(WatchedRounds):
         self.t.broadcast_from_server(self.image_wire.buf)
         return self._gs_after_fetch()
 
+    delta = None        # this rank's worker end of the delta wire (--fetch-codec q8delta)
+    _delta_keyed = False
+
+    def _receiver(self):
+        if self.delta is None:
+            from .fetchq8 import Receiver
+
+            self.delta = Receiver(self.codec.layout, self.codec.device)
+        return self.delta
+
+    def _fetch_delta(self, local_arena):
+        """--fetch-codec q8delta (parallel/fetchq8.py). This channel's first round is the keyframe
+        (every rank knows that from the round number alone, so the collective sequence stays in
+        lockstep): the fp32 broadcast of the plain fetch. Every later round broadcasts the payload
+        of arena - shadow, and each remote worker adds what it decodes to. Rank 0's co-located
+        worker takes its weights from the shadow, the bits every other worker computes on, not
+        from the fp32 master. ``bytes_fetched``: per worker on another rank."""
+        key, self._delta_keyed = not self._delta_keyed, True
+        if self.server is not None:
+            s = self.server
+            for w in self.members:
+                s.core.on_fetch(w)
+            _, _, payload = s.fetch_delta(keyframe=key)
+            wire = s.shadow if key else payload
+            self.t.broadcast_from_server(wire)
+            s.bytes_fetched += wire.numel() * wire.element_size() * (len(self.members) - int(self.root_worker))
+            if local_arena is not None:
+                local_arena.copy_(s.shadow)
+                self._receiver().keyframe(local_arena)
+            return s.core.global_step
+        self._receiver()
+        if key:
+            self.t.broadcast_from_server(local_arena)
+            self.delta.keyframe(local_arena)
+        else:
+            self.t.broadcast_from_server(self.delta.payload)
+            self.delta.apply(local_arena)
+        return self._gs_after_fetch()
+
     def _fetch(self, worker_id, local_arena):
         if self.image:
             return self._fetch_image()
+        if self.codec is not None and self.codec.kind == "q8delta":
+            return self._fetch_delta(local_arena)
         if self.server is not None:
             for w in self.members:
                 self.server.core.on_fetch(w)
@@ -590,6 +659,10 @@ class Worker:
             "last_loss": round(self.losses[-1], 4) if self.losses else None,
             "rank": self.rank,
         }
+        delta = getattr(self.channel, "delta", None)
+        if self.cfg.fetch_codec == "q8delta" and delta is not None and delta.bufs is not None:
+            # the state as last fetched: equal on every worker and to the server's fetch_shadow_sha256
+            rec["local_arena_sha256"] = delta.state_sha256(self.compute.local_arena)
         self.log(f"\n--- Worker {self.worker_id} Statistics ---\nTotal training time: {total:.1f} seconds\n"
                  f"Local steps completed: {self.local_step_counter}\n--- End Statistics ---")
         M.emit(rec, self.cfg.log_dir, rank=self.rank)

@@ -109,7 +109,9 @@ class PSConfig:
     # PSX_DETERMINISTIC (default 1 = on; engine)
     # fetch payload: "bf16conv" = conv weights as bf16 (exactly the bits the bf16 engine consumes)
     # + fp32 for everything else (half the bytes); "fp32" = the reference's full fp32 state;
-    # "auto" = fp32 for --dtype fp32, bf16conv for --dtype bf16.
+    # "auto" = fp32 for --dtype fp32, bf16conv for --dtype bf16; "q8delta" = after one fp32 keyframe,
+    # the block-scaled int8 of what changed since the workers' copy (1.016 bytes per element, error
+    # feedback; parallel/fetchq8.py). Sync mode, rank-0 server, serial rounds, either --dtype.
     fetch_codec: str = "auto"
     # sync rounds stream gradient buckets during the backward pass (parallel/overlap.py). None =
     # auto: on with >= 2 ranks (the gather / apply / broadcast of the first buckets hides under
@@ -221,9 +223,20 @@ class PSConfig:
             raise ValueError(f"--dtype must be fp32 or bf16, got {self.dtype!r}")
         if self.fetch_codec == "auto":
             self.fetch_codec = "fp32" if self.dtype == "fp32" else "bf16conv"
-        if self.fetch_codec not in ("bf16conv", "fp32"):
-            raise ValueError("--fetch-codec must be bf16conv or fp32")
-        if self.dtype == "fp32" and self.fetch_codec != "fp32":
+        if self.fetch_codec not in ("bf16conv", "fp32", "q8delta"):
+            raise ValueError("--fetch-codec must be bf16conv, fp32 or q8delta")
+        if self.fetch_codec == "q8delta":  # parallel/fetchq8.py scope
+            if self.mode != "sync":
+                raise ValueError("--fetch-codec q8delta keeps one shadow of the workers' copy, which only lockstep "
+                                 "rounds keep equal on every worker: --mode sync only (async would need a shadow "
+                                 "per worker)")
+            if self.topology == "sharded":
+                raise ValueError("--fetch-codec q8delta encodes the whole arena on a rank-0 server: not with "
+                                 "--topology sharded (its fetch is an all-gather of per-rank ranges)")
+            if self.overlap is True:
+                raise ValueError("--fetch-codec q8delta encodes the arena once it is final: not with --overlap "
+                                 "(a bucketed round broadcasts each bucket before the others are applied)")
+        if self.dtype == "fp32" and self.fetch_codec == "bf16conv":
             raise ValueError("--fetch-codec bf16conv ships bf16 conv weights, which only the bf16 engine consumes: "
                              "add --dtype bf16 (the default since round 2 is --dtype fp32, the reference's "
                              "precision, whose fetch payload is the fp32 state)")
@@ -243,10 +256,12 @@ class PSConfig:
         with and the round qualifies (sync, one push per batch, dense wire, rank-0 server). The
         error-feedback codecs (q8, sign1, topk) encode the whole gradient at once, and a whole-arena update
         (whole_arena_update) cannot start before the last bucket: no bucketed rounds. --optimizer
-        adamw is element-wise and stays eligible."""
+        adamw is element-wise and stays eligible. --fetch-codec q8delta encodes the final arena of a
+        round, which a bucketed round broadcasts piecewise before it exists: no bucketed rounds."""
         if self.overlap is None:
             self.overlap = (world > 1 and self.mode == "sync" and max(1, self.sync_steps) == 1
-                            and self.dense_wire and self.topology != "sharded" and not self.whole_arena_update)
+                            and self.dense_wire and self.topology != "sharded" and not self.whole_arena_update
+                            and self.fetch_codec != "q8delta")
         return bool(self.overlap)
 
     @property
@@ -331,7 +346,10 @@ def add_arguments(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
            "+0-2%% step time, profiles/r5_deterministic_ab.jsonl)")
     A("--no-deterministic", dest="deterministic", action="store_false", default=None,
       help="float-atomic BN statistic reductions (order-dependent rounding)")
-    A("--fetch-codec", choices=["auto", "bf16conv", "fp32"], default=None)
+    A("--fetch-codec", choices=["auto", "bf16conv", "fp32", "q8delta"], default=None,
+      help="fetch wire: fp32 (the whole state), bf16conv (bf16 conv weights, --dtype bf16) or q8delta (sync, rank-0 "
+           "server: one fp32 keyframe, then the block-scaled int8 of what changed since the workers' copy, 1.016 "
+           "B/element with error feedback); auto = fp32 for --dtype fp32, bf16conv for --dtype bf16")
     A("--overlap", dest="overlap", action="store_true", default=None,
       help="sync mode: stream gradient buckets (reduce/apply/broadcast) during the backward pass")
     A("--no-overlap", dest="overlap", action="store_false", default=None)

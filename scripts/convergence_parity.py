@@ -15,6 +15,10 @@
                       torch seed-to-seed spread.
 * ``psx_fp32_sign1``  the same with the 1-bit sign wire and error feedback (--codec sign1); compared
                       against ``psx_fp32`` in the same way (``sign1_vs_psx_fp32``).
+* ``psx_fp32_q8delta`` psx_fp32 with the delta-quantised int8 fetch wire (--fetch-codec q8delta): the worker
+                      computes on the server's shadow, not on the fp32 master; compared against
+                      ``psx_fp32`` (``q8delta_vs_psx_fp32``), next to the torch seed-to-seed spread,
+                      recorded and not asserted.
 * ``psx_fp32_lars``   psx_fp32 with the layer-wise adaptive server optimizer (--optimizer lars, momentum
                       0.9, weight decay 5e-4, trust 0.001, lr ``--lars-lr``, default 2.0: the
                       trust ratio scales every tensor's step to lr * 0.001 * |w| / |g|, so its lr is
@@ -92,7 +96,8 @@ def run_psx(args, train, test, dtype: str, codec: str, bn_sync: bool = True, **o
     """bn_sync: the worker pushes its BN running statistics with the gradient (W = 1: the server
     keeps the worker's, as a single-process trainer does); without it the reference semantics
     apply (every fetch resets them to the server's never-updated copy). ``opt``: server optimizer
-    fields of PSConfig (optimizer, lr, momentum, weight_decay) overriding the plain SGD at --lr."""
+    fields of PSConfig (optimizer, lr, momentum, weight_decay) overriding the plain SGD at --lr, or
+    its fetch_codec."""
     cfg = PSConfig(**{**dict(model="resnet18", mode="sync", workers=1, lr=args.lr, batch_size=args.batch,
                              epochs=10 ** 6, train_samples=args.train, eval_every=0, verbose=0, dtype=dtype,
                              codec=codec, bn_sync=bn_sync), **opt}).validate()
@@ -230,6 +235,7 @@ def main():
                      ("psx_fp32_wire32", lambda: run_psx(args, train, test, "fp32", "none")),
                      ("psx_fp32_q8", lambda: run_psx(args, train, test, "fp32", "q8")),
                      ("psx_fp32_sign1", lambda: run_psx(args, train, test, "fp32", "sign1")),
+                     ("psx_fp32_q8delta", lambda: run_psx(args, train, test, "fp32", "fp16", fetch_codec="q8delta")),
                      ("psx_fp32_lars", lambda: run_psx(args, train, test, "fp32", "fp16", **lars)),
                      ("psx_fp32_adamw", lambda: run_psx(args, train, test, "fp32", "fp16", **adamw)),
                      ("psx_fp32_lamb", lambda: run_psx(args, train, test, "fp32", "fp16", **lamb)),
@@ -254,8 +260,8 @@ def main():
                      "test_acc_diff_pp": r["test_acc"] - runs["torch_fp32"]["test_acc"]}
         print(f"  vs torch_fp32: {name:18s} {json.dumps(cmp[name])}", flush=True)
     vs_psx = {}
-    for name in ("psx_fp32_q8", "psx_fp32_sign1", "psx_fp32_lars", "psx_fp32_adamw", "psx_fp32_lamb",
-                 "psx_fp32_lars_warmup"):
+    for name in ("psx_fp32_q8", "psx_fp32_sign1", "psx_fp32_q8delta", "psx_fp32_lars", "psx_fp32_adamw",
+                 "psx_fp32_lamb", "psx_fp32_lars_warmup"):
         if name not in runs or "psx_fp32" not in runs:
             continue
         d = smooth(runs[name]["loss"], args.window) - smooth(runs["psx_fp32"]["loss"], args.window)
@@ -275,6 +281,7 @@ def main():
                                           "20% label noise, 100 classes",
            "runs": runs, "vs_torch_fp32": cmp, "q8_vs_psx_fp32": vs_psx.get("psx_fp32_q8"),
            "sign1_vs_psx_fp32": vs_psx.get("psx_fp32_sign1"),
+           "q8delta_vs_psx_fp32": vs_psx.get("psx_fp32_q8delta"),
            "lars_vs_psx_fp32": vs_psx.get("psx_fp32_lars"), "adamw_vs_psx_fp32": vs_psx.get("psx_fp32_adamw"),
            "lamb_vs_psx_fp32": vs_psx.get("psx_fp32_lamb"),
            "lars_warmup_vs_psx_fp32": vs_psx.get("psx_fp32_lars_warmup"),
