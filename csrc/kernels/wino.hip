@@ -40,6 +40,11 @@ extern "C" int psx_bgemm_f32_split(const float* A, const float* B, float* P, con
                                    int nb, int s2, int cfg, hipStream_t st);
 extern "C" int psx_wino_wout(const float* part, void* out, int out_fp16, float scale, int K, int C, int q,
                              hipStream_t st);
+extern "C" int psx_wino_conv_pre(const float* V, const float* U, float* y, const float* res, float* stats, float* P,
+                                 const void* zero, int N, int H, int W, int C, int K, int cfg,
+                                 const psx::WinoBwdStats* bst, const float* sshift, hipStream_t st);
+extern "C" int psx_wino_wgrad_pre(const float* V, const float* D, float* part, void* out, int out_fp16, float scale,
+                                  const void* zero, int N, int H, int W, int C, int K, hipStream_t st);
 extern "C" int psx_bgemm_tn_f32(const float* X, const float* D, float* part, const void* zero, int T, int C, int K,
                                 int nb, int q, int BR, int BC, hipStream_t st);
 
@@ -168,6 +173,11 @@ __global__ __launch_bounds__(64) void wino_w_multi_kernel(WinoWBatch bt) {
 // results over LDS (double-buffered: one barrier per tile), and wave s then applies the column
 // transform to column s and stores it (6 stores). 6x the waves, 1/6 of the chain per wave, the
 // next tile's row prefetched behind the current tile's transform.
+// Kernels: wino_in_xf (V of a forward / data-gradient input), wino_dy_xf (D of a weight gradient's
+// dy), wino_dz_xf (a backward's V' and D from one read of dz: the 4x4 dy tile is the inner part of
+// the 6x6 window, so waves 1-4 feed both transforms from the row they loaded; the engine's
+// backward of the three-launch layers, the other two remain for the forward and for the weight
+// gradients on a side stream), wino_out_xf, wino_wout_xf.
 constexpr int kXfWaves = 6;
 
 // grid.y of the split kernels: ~4 workgroups per CU over the channel blocks, at most a tile each
@@ -325,6 +335,120 @@ __global__ __launch_bounds__(384) void wino_dy_xf_kernel(const float* __restrict
     __syncthreads();
     float col[4] = {xf[p][0][wv][lane], xf[p][1][wv][lane], xf[p][2][wv][lane], xf[p][3][wv][lane]}, o[6];
     wino_a4(col, o);
+    float* dt = D + (size_t)t * K + k;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) dt[(r * 6 + wv) * bs] = o[r];
+  }
+}
+
+// Backward of a three-launch layer, both operands of dz in one pass: V'[b][t][k] = B^T dy B of the
+// 6x6 window (wino_in_xf_kernel's arithmetic) and D[b][t][k] = A dy A^T of its inner 4x4 tile
+// (wino_dy_xf_kernel's), bit for bit what the two kernels write. FOLD != kDzPlain: dz is the
+// input of a BN backward whose apply was never run, dy = k1 dz + k2 ybn + k3 formed in the load,
+// the coefficients from the slot rows bpart (wino_bwd_coef); the workgroups of grid row 0
+// publish them with dgamma / dbeta (as wino_fused.hip's backward-input prologue). kDzShared rounds
+// dy as wino_bwd_apply (what wino_dy_xf_kernel's and the fused kernels' folds form), kDzApply as
+// the apply pass it replaces (bn_bwd_apply_bits): V' and D are then the plain transforms of the dy
+// that pass would have written, which is what the engine runs — its step stays bit-equal to the
+// unfolded one and to the side-stream path that still writes dy. Padding is
+// zeroed after the fold (k3 would leak into it), which is also wino_dy_xf_kernel's rule for the
+// rows and columns of a partial edge tile outside the image: both transforms read one window.
+// The B^T passes use wino_bt6_fused: its <true> form is the contraction hipcc gives
+// wino_in_xf_kernel's row pass and <false> the one of its column pass (r[0]: which product of
+// 4 d0 - 5 d2 is the fused one), pinned here so the merged kernel cannot drift from it.
+constexpr int kDzPlain = 0, kDzShared = 1, kDzApply = 2;
+template <int FOLD>
+__global__ __launch_bounds__(384) void wino_dz_xf_kernel(const float* __restrict__ dz, float* __restrict__ V,
+                                                         float* __restrict__ D, int T, int H, int W, int K,
+                                                         const float* __restrict__ ybn,
+                                                         const float* __restrict__ bpart, BnBwdFin bfin) {
+  __shared__ float xf[2][6][6][64];
+  __shared__ float xa[2][4][6][64];
+  __shared__ float kc[3][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int k = blockIdx.x * 64 + lane;
+  const int tw = (W + 3) >> 2, tpi = ((H + 3) >> 2) * tw;  // partial edge tiles
+  const size_t bs = (size_t)T * K;
+  constexpr bool BWD = FOLD != kDzPlain;
+  float k1 = 1.f, k2 = 0.f, k3 = 0.f;
+  if constexpr (BWD) {
+    if (wv == 0) {
+      double sdz, sxh;
+      wino_bwd_coef(bpart, bfin, k, k1, k2, k3, sdz, sxh);
+      kc[0][lane] = k1;
+      kc[1][lane] = k2;
+      kc[2][lane] = k3;
+      if (blockIdx.y == 0) {  // one grid row publishes the coefficients and dgamma / dbeta (the wire)
+        bfin.coef[k] = k1;
+        bfin.coef[K + k] = k2;
+        bfin.coef[2 * K + k] = k3;
+        const float dg = (float)sxh * bfin.gscale, db = (float)sdz * bfin.gscale;
+        if (bfin.grad_fp16) {
+          reinterpret_cast<uint16_t*>(bfin.dgamma)[k] = __builtin_bit_cast(uint16_t, (_Float16)dg);
+          reinterpret_cast<uint16_t*>(bfin.dbeta)[k] = __builtin_bit_cast(uint16_t, (_Float16)db);
+        } else {
+          reinterpret_cast<float*>(bfin.dgamma)[k] = dg;
+          reinterpret_cast<float*>(bfin.dbeta)[k] = db;
+        }
+      }
+    }
+    __syncthreads();
+    k1 = kc[0][lane];
+    k2 = kc[1][lane];
+    k3 = kc[2][lane];
+  }
+  auto load = [&](int t, float (&d)[6], float (&yv)[6], unsigned& okc, bool& okr) {
+    const int n = t / tpi, rem = t - n * tpi, ti = rem / tw, tj = rem - ti * tw;
+    const int h = 4 * ti - 1 + wv, w0 = 4 * tj - 1;
+    okr = (unsigned)h < (unsigned)H;
+    okc = 0;
+    const size_t row = ((size_t)n * H + (okr ? h : 0)) * W * K + k;
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+      const bool ok = (unsigned)(w0 + s) < (unsigned)W;
+      okc |= (unsigned)ok << s;
+      const size_t off = row + (size_t)(ok ? w0 + s : 0) * K;  // in bounds (zeroed below when padding)
+      d[s] = dz[off];
+      if constexpr (BWD) yv[s] = ybn[off];
+    }
+  };
+  int t = blockIdx.y;
+  float d[6], yv[6];
+  unsigned okc = 0;
+  bool okr = false;
+  if (t < T) load(t, d, yv, okc, okr);
+  for (int p = 0; t < T; t += gridDim.y, p ^= 1) {
+    float cur[6];
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+      float v = d[s];
+      if constexpr (FOLD == kDzShared) v = wino_bwd_apply(v, yv[s], k1, k2, k3);
+      if constexpr (FOLD == kDzApply) v = bn_bwd_apply_bits(v, yv[s], k1, k2, k3);
+      cur[s] = (okr && ((okc >> s) & 1u)) ? v : 0.f;
+    }
+    const int tn = t + gridDim.y;
+    if (tn < T) load(tn, d, yv, okc, okr);
+    float e[6];  // row wv of dy B
+    wino_bt6_fused<true>(cur, e);
+#pragma unroll
+    for (int s = 0; s < 6; ++s) xf[p][wv][s][lane] = e[s];
+    if (wv >= 1 && wv <= 4) {  // window rows 1..4 are the 4x4 dy tile's: row wv - 1 of dy A^T
+      const float y4[4] = {cur[1], cur[2], cur[3], cur[4]};
+      float a[6];
+      wino_a4(y4, a);
+#pragma unroll
+      for (int s = 0; s < 6; ++s) xa[p][wv - 1][s][lane] = a[s];
+    }
+    __syncthreads();
+    float col[6], o[6];  // column wv of (dy B): B^T applied
+#pragma unroll
+    for (int r = 0; r < 6; ++r) col[r] = xf[p][r][wv][lane];
+    wino_bt6_fused<false>(col, o);
+    float* vt = V + (size_t)t * K + k;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) vt[(r * 6 + wv) * bs] = o[r];
+    const float c4[4] = {xa[p][0][wv][lane], xa[p][1][wv][lane], xa[p][2][wv][lane], xa[p][3][wv][lane]};
+    wino_a4(c4, o);  // column wv of (dy A^T): A applied
     float* dt = D + (size_t)t * K + k;
 #pragma unroll
     for (int r = 0; r < 6; ++r) dt[(r * 6 + wv) * bs] = o[r];
@@ -606,6 +730,16 @@ int psx_wino_conv(const float* x, const float* U, float* y, const float* res, fl
   bf.det = (int)det_enabled();
   hipLaunchKernelGGL(wino_in_xf_kernel, dim3(C / 64, wino_xf_grid(T, C / 64)), dim3(64 * kXfWaves), 0, st, x, V, T, H,
                      W, C, bnpart, bf);
+  return psx_wino_conv_pre(V, U, y, res, stats, P, zero, N, H, W, C, K, cfg, bst, sshift, st);
+}
+
+// psx_wino_conv from an already transformed input V [36][T][C] (psx_wino_dz_xf wrote it): the 36
+// GEMMs and the output transform, no input-transform launch.
+int psx_wino_conv_pre(const float* V, const float* U, float* y, const float* res, float* stats, float* P,
+                      const void* zero, int N, int H, int W, int C, int K, int cfg, const WinoBwdStats* bst,
+                      const float* sshift, hipStream_t st) {
+  if (!psx_wino_ok(H, W, C, K)) return -2;
+  const int T = (int)wino_tiles(N, H, W);
   // the 36 GEMMs: the conv_v2 mainloop. (Measured slower and removed in round 5: a stream-K GEMM,
   // 8x8x256 40.6 vs 33.7 us, profiles/r4_sk_gemm_probes.jsonl; the GEMM with the output transform
   // in its epilogue, 64 output registers per accumulator forcing 16x16 wave tiles: neutral where
@@ -670,10 +804,55 @@ int psx_wino_wgrad(const float* V, const float* dy, float* D, float* part, void*
   bb.det = (int)det_enabled();
   hipLaunchKernelGGL(wino_dy_xf_kernel, dim3(K / 64, wino_xf_grid(T, K / 64)), dim3(64 * kXfWaves), 0, st, dy, D, T, H,
                      W, K, ybn, bpart, bb);
+  return psx_wino_wgrad_pre(V, D, part, out, out_fp16, scale, zero, N, H, W, C, K, st);
+}
+
+// psx_wino_wgrad from an already transformed D [36][T][K] (psx_wino_dz_xf wrote it): the batched
+// TN GEMM and the output transform, no dy-transform launch.
+int psx_wino_wgrad_pre(const float* V, const float* D, float* part, void* out, int out_fp16, float scale,
+                       const void* zero, int N, int H, int W, int C, int K, hipStream_t st) {
+  const int q = psx_wino_wgrad_q(N, H, W, C, K);
+  if (q < 1) return -2;
+  const int T = (int)wino_tiles(N, H, W);
   const int bt = wino_wtile(C, K);
   int e = psx_bgemm_tn_f32(V, D, part, zero, T, C, K, 36, q, bt, bt, st);
   if (e) return e;
   return psx_wino_wout(part, out, out_fp16, scale, K, C, q, st);
+}
+
+// 1 when psx_wino_dz_xf takes dz [N][H][W][K]: what the transforms ask of a shape (psx_wino_ok).
+// Whether the GEMMs take its outputs is theirs to say (psx_wino_wgrad_q: whole 32-tile ranges).
+int psx_wino_dz_ok(int N, int H, int W, int K) { return N > 0 && psx_wino_ok(H, W, K, K); }
+
+// Both backward operands of a three-launch layer from ONE pass over dz [N][H][W][K]
+// (wino_dz_xf_kernel): V [36][T][K], the data gradient's transformed input (psx_wino_conv_pre),
+// and D [36][T][K], the weight gradient's (psx_wino_wgrad_pre). ybn / bpart / bbfin (nullable, as
+// psx_wino_wgrad): dz is the input of a BN backward folded into the load; this launch also
+// publishes that BN's coefficients and dgamma / dbeta. -2: not this shape, -3: inconsistent fold.
+// as_apply: the fold rounds dy as the apply pass would have (kDzApply) instead of as the other
+// folded consumers do (kDzShared).
+static int wino_dz_xf(const float* dz, float* V, float* D, int N, int H, int W, int K, const float* ybn,
+                      const float* bpart, const BnBwdFin* bbfin, bool as_apply, hipStream_t st) {
+  if (!psx_wino_dz_ok(N, H, W, K)) return -2;
+  if (bpart ? (!ybn || !bbfin || bbfin->C != K) : (ybn != nullptr)) return -3;
+  const int T = (int)wino_tiles(N, H, W);
+  BnBwdFin bb{};
+  if (bpart) bb = *bbfin;
+  bb.det = (int)det_enabled();
+  const dim3 grid(K / 64, wino_xf_grid(T, K / 64)), block(64 * kXfWaves);
+  auto* kern = !bpart ? wino_dz_xf_kernel<kDzPlain> : as_apply ? wino_dz_xf_kernel<kDzApply> : wino_dz_xf_kernel<kDzShared>;
+  hipLaunchKernelGGL(kern, grid, block, 0, st, dz, V, D, T, H, W, K, ybn, bpart, bb);
+  return (int)hipGetLastError();
+}
+
+int psx_wino_dz_xf(const float* dz, float* V, float* D, int N, int H, int W, int K, const float* ybn,
+                   const float* bpart, const BnBwdFin* bbfin, hipStream_t st) {
+  return wino_dz_xf(dz, V, D, N, H, W, K, ybn, bpart, bbfin, false, st);
+}
+
+int psx_wino_dz_xf_as_apply(const float* dz, float* V, float* D, int N, int H, int W, int K, const float* ybn,
+                            const float* bpart, const BnBwdFin* bbfin, hipStream_t st) {
+  return wino_dz_xf(dz, V, D, N, H, W, K, ybn, bpart, bbfin, true, st);
 }
 
 // dW[k][c][3][3] = scale * G^T M G with M[b] = sum_j part[b * q + j][k][c]: the output transform

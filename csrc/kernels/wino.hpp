@@ -112,4 +112,12 @@ PSX_DEV void wino_bwd_coef(const float* part, const BnBwdFin& f, int c, float& k
 // the folded operand: dx = k1 dz + k2 y + k3 (one rounding order for every consumer)
 PSX_DEV float wino_bwd_apply(float dz, float y, float k1, float k2, float k3) { return fmaf(k1, dz, fmaf(k2, y, k3)); }
 
+// the same operand with the rounding of bn.hip's apply kernels (bn_bwd_apply_fin_kernel: the
+// product k2 y rounded, k1 dz fused onto it, k3 added last): a consumer that folds with this one
+// reads the bits the apply pass would have written, so its step equals the unfolded one bit for bit
+PSX_DEV float bn_bwd_apply_bits(float dz, float y, float k1, float k2, float k3) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(k1, dz, k2 * y) + k3;
+}
+
 }  // namespace psx

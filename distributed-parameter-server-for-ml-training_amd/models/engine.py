@@ -425,6 +425,8 @@ class HipResNetEngine:
         self.wino_wgf = set()   # weight gradient by the fused kernel (wino_wgrad.hip): reads x, not V
         self.wino_bnfold = {}
         self.wino_fused = {}
+        self.wino_dz = set()    # three-launch layers whose backward transforms dz once (wino_dz_xf)
+        self._dz_pre = None
         self._xfold = {}        # conv -> (pre-BN y, BN affine): its input is relu(BN(y)), never written
         if not self.f32 or not tune_flag("wino", True):
             return
@@ -472,6 +474,14 @@ class HipResNetEngine:
                 else:
                     s_d = max(s_d, vk)
                     s_part = max(s_part, 36 * q * cs.cout * cs.cp)
+                    # one pass over dz forms both backward operands (wino.hip wino_dz_xf_kernel): D
+                    # for the weight gradient and V' for the data gradient, instead of a dy
+                    # transform and an input transform that each read dy. Only with both
+                    # gradients on the compute stream: on the side stream D would be written into
+                    # scratch that stream still reads.
+                    if (self.wg_stream is None and cs.need_dgrad and not fd
+                            and K.wino_dz_ok(B, cs.h, cs.w, cs.cout)):
+                        self.wino_dz.add(cs.name)
         # BN folded into the next conv's input transform (PSX_TUNE wino_bnfold=1, default): a block's inner
         # BN (+ ReLU) whose only consumer is a Winograd conv with a Winograd weight gradient (that
         # reads V, not the activation) is finalized and applied inside wino_in_kernel, so its
@@ -707,6 +717,17 @@ class HipResNetEngine:
             K.wino_wgrad_fused(xf[0] if xf else x, dy, wpart, self.layout.grad_view(self.grads, f"{cs.name}.weight"),
                                self.B, cs.h, cs.w, cs.cp, cs.cout, xaff=xf[1] if xf else None, bwd_in=fold)
             return
+        if cs.name in self.wino_dz and scratch is None:
+            # both operands from one pass over dy (with ``fold``: over dz, the BN apply folded in
+            # and its coefficients published): D here, V' left in wino_s1 for _dgrad, which
+            # follows; nothing of the weight-gradient chain touches wino_s1
+            # rounded as the apply pass (as_apply): the step equals the unfolded one bit for bit
+            K.check(K.wino_dz_xf(dy, self.wino_s1, self.wino_wd, self.B, cs.h, cs.w, cs.cout, bwd_in=fold,
+                                 as_apply=True), "wino_dz_xf")
+            self._dz_pre = cs.name
+            K.wino_wgrad_pre(self.wino_layers[cs.name][2], self.wino_wd, self.wino_wpart,
+                             self.layout.grad_view(self.grads, f"{cs.name}.weight"), self.B, cs.h, cs.w, cs.cp, cs.cout)
+            return
         if cs.name in self.wino_wgrad:  # straight into the wire: no split partials to reduce
             wd, wpart = scratch if scratch is not None else (self.wino_wd, self.wino_wpart)
             K.wino_wgrad(self.wino_layers[cs.name][2], dy, wd, wpart,
@@ -763,7 +784,12 @@ class HipResNetEngine:
             if self.wino_fused[cs.name][1]:
                 K.wino_fused(dy, wl[1], dx, res, None, None, self.B, cs.h, cs.w, cs.cout, cs.cp, bst=bst,
                              bwd_in=self._bwd_fold.get(cs.name))
+            elif self._dz_pre == cs.name:  # its transformed input is in wino_s1 already (_wgrad_now)
+                self._dz_pre = None
+                K.wino_conv_pre(self.wino_s1, wl[1], dx, res, None, self.wino_s2, self.B, cs.h, cs.w, cs.cout,
+                                cs.cp, bst=bst)
             else:
+                assert cs.name not in self._bwd_fold, cs.name  # a folded dy exists in no buffer
                 K.wino_conv(dy, wl[1], dx, res, None, self.wino_s1, self.wino_s2, self.B, cs.h, cs.w, cs.cout,
                             cs.cp, bst=bst)
             return
@@ -787,9 +813,12 @@ class HipResNetEngine:
         weight gradient, g is already the masked dz and its sums came from the producing dgrad's
         epilogue): no apply pass — dy = k1 dz + k2 y + k3 is formed inside both consumers'
         operand loads (wino_fused.hip, wino.hip dy transform), and the fused data gradient
-        publishes the coefficients and dgamma / dbeta."""
+        publishes the coefficients and dgamma / dbeta. A three-launch layer in ``wino_dz`` folds
+        too: its one pass over dz (wino.hip wino_dz_xf_kernel) is both consumers' load and the
+        publisher, and rounds dy as the apply pass would (bit-equal to the unfolded step)."""
         ok = (self.bwd_fold and self._fold and bs.name in self._premasked and bs.name in self._prereduced
-              and cs.name in self.wino_wgrad and self.wino_fused.get(cs.name, (False, False))[1])
+              and cs.name in self.wino_wgrad
+              and (self.wino_fused.get(cs.name, (False, False))[1] or cs.name in self.wino_dz))
         if not ok:
             dz = self._bn_bwd(bs, arena, g, o, y, dx, npix, dzout=dzout)
             return dz, dx

@@ -67,6 +67,11 @@ _KERNEL_SIGS = {
     "psx_wino_p_floats": (i64, [i32, i32, i32, i32, i32]),
     "psx_wino_wgrad_q": (i32, [i32, i32, i32, i32, i32]),
     "psx_wino_wgrad": (i32, [vp, vp, vp, vp, vp, i32, f32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "psx_wino_conv_pre": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "psx_wino_wgrad_pre": (i32, [vp, vp, vp, vp, i32, f32, vp, i32, i32, i32, i32, i32, vp]),
+    "psx_wino_dz_ok": (i32, [i32, i32, i32, i32]),
+    "psx_wino_dz_xf": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "psx_wino_dz_xf_as_apply": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "psx_bgemm_tn_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "psx_wino_wout": (i32, [vp, vp, i32, f32, i32, i32, i32, vp]),
     "psx_wino_wgrad_fused_q": (i32, [i32, i32, i32, i32, i32]),

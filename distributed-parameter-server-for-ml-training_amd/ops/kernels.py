@@ -358,6 +358,54 @@ def wino_wgrad(v, dy, d, part, out, nb, h, w, c, k, scale=1.0, bwd_in=None):
                                    C.byref(bwd_in[2]) if bwd_in is not None else None, stream_ptr()), "wino_wgrad")
 
 
+def wino_dz_ok(nb, h, w, k) -> bool:
+    """wino_dz_xf takes dz [nb][h][w][k] (wino_ok of k channels; any tile count)."""
+    return bool(kernels().psx_wino_dz_ok(nb, h, w, k))
+
+
+def wino_dz_xf(dz, v, d, nb, h, w, k, bwd_in=None, as_apply=False) -> int:
+    """Both backward operands of a three-launch Winograd layer from one pass over dz [nb][h][w][k]
+    (wino.hip wino_dz_xf_kernel): v = the data gradient's transformed input (for wino_conv_pre), d
+    = the weight gradient's transformed dy (for wino_wgrad_pre), each >= wino_v_floats(k), bit for
+    bit what wino_conv and wino_wgrad form themselves. bwd_in = (y, part, BnBwdFin): dz is the
+    input of a BN backward whose apply is folded into the load (as wino_wgrad's); this launch also
+    writes the BnBwdFin's coefficients and dgamma / dbeta. as_apply: the folded dy is rounded as
+    bn_bwd_apply_fin writes it (v and d are then bit for bit the transforms of that dy) instead
+    of as wino_wgrad's and wino_fused's folds round it. Returns the entry's code: 0, -2 for a
+    shape it refuses (not wino_dz_ok), -3 for inconsistent fold arguments; nothing is launched then."""
+    assert dz.dtype == v.dtype == d.dtype == torch.float32 and dz.numel() == nb * h * w * k
+    assert min(v.numel(), d.numel()) >= wino_v_floats(nb, h, w, k)
+    y, part, fin = bwd_in if bwd_in is not None else (None, None, None)
+    fn = kernels().psx_wino_dz_xf_as_apply if as_apply else kernels().psx_wino_dz_xf
+    return int(fn(ptr(dz), ptr(v), ptr(d), nb, h, w, k, ptr(y), ptr(part), C.byref(fin) if fin is not None else None,
+                  stream_ptr()))
+
+
+def wino_conv_pre(v, u, y, res, stats, p, nb, h, w, c, k, cfg=None, bst: "BwdStatsDesc | None" = None, sshift=None):
+    """wino_conv from an already transformed input v [36][T][c] (wino_dz_xf): the GEMMs and the
+    output transform only. The other arguments as wino_conv."""
+    assert v.dtype == torch.float32 and y.dtype == torch.float32
+    assert y.numel() == nb * h * w * k and u.numel() >= 36 * k * c
+    assert v.numel() >= wino_v_floats(nb, h, w, c) and p.numel() >= wino_p_floats(nb, h, w, c, k)
+    assert res is None or res.numel() == y.numel()
+    check(kernels().psx_wino_conv_pre(ptr(v), ptr(u), ptr(y), ptr(res), ptr(stats), ptr(p), ptr(zero_page(v.device)),
+                                      nb, h, w, c, k, 0 if cfg is None else cfg,
+                                      C.byref(bst) if bst is not None else None, ptr(sshift), stream_ptr()),
+          "wino_conv_pre")
+
+
+def wino_wgrad_pre(v, d, part, out, nb, h, w, c, k, scale=1.0):
+    """wino_wgrad from an already transformed dy, d [36][T][k] (wino_dz_xf): the batched GEMM and
+    the output transform only. The other arguments as wino_wgrad."""
+    q = wino_wgrad_q(nb, h, w, c, k)
+    assert q > 0 and d.dtype == torch.float32
+    assert d.numel() >= wino_v_floats(nb, h, w, k) and part.numel() >= 36 * q * k * c
+    assert out.dtype in (torch.float16, torch.float32) and out.numel() >= k * c * 9
+    check(kernels().psx_wino_wgrad_pre(ptr(v), ptr(d), ptr(part), ptr(out), int(out.dtype == torch.float16),
+                                       float(scale), ptr(zero_page(d.device)), nb, h, w, c, k, stream_ptr()),
+          "wino_wgrad_pre")
+
+
 def wino_wgrad_fused_q(nb, h, w, c, k) -> int:
     """Tile ranges of the fused Winograd weight gradient (csrc/kernels/wino_wgrad.hip; 0: not
     applicable): its partial slabs take 36 * q * k * c floats."""
