@@ -6,6 +6,8 @@
 //   | q:      int8[n],    section padded to a multiple of 16 bytes ]
 // Blocks are runs of 256 consecutive elements of the flat parameter arena and are independent:
 // every entry point takes a 256-aligned element sub-range [off, off + cnt).
+// The frame (layout, range check, gradient loaders, header write, the source list and the two
+// forms of the update from payloads) is blockwire.hpp's; here is the codec's arithmetic.
 //
 // Arithmetic per block, acc = resid + float(g) (fixed: the torch CPU path of parallel/q8.py
 // follows it literally and both agree bit for bit):
@@ -27,9 +29,7 @@
 //                      per source (4 rows of a wave's 1024 elements), same update tail as
 //                      sgd_apply_multi (sgd_tail.hpp)
 //   * q8_decode      : dst = [dst +] scale * deq (in-process accumulation, reference semantics)
-#include <float.h>
-
-#include "wire.hpp"
+#include "blockwire.hpp"
 
 // Everything below keeps its multiplies and adds apart (hipcc contracts by default); the shared
 // update tail above was parsed with the library default, as in optim.hip.
@@ -37,36 +37,10 @@
 
 namespace psx {
 
-constexpr int kQ8Block = 256;
 constexpr int kQ8Magic = 0x31423851;  // the bytes 'Q' '8' 'B' '1'
 
-struct Q8Layout {
-  long nblk, scales_off, q_off, bytes;
-};
-static inline Q8Layout q8_layout(long n) {
-  Q8Layout l;
-  l.nblk = (n + kQ8Block - 1) / kQ8Block;
-  l.scales_off = 16;
-  l.q_off = l.scales_off + ((4 * l.nblk + 15) & ~15L);
-  l.bytes = l.q_off + ((n + 15) & ~15L);
-  return l;
-}
-
-PSX_DEV float h2f(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (uint16_t)bits); }
-PSX_DEV float ld_g1(const float* g, long i) { return g[i]; }
-PSX_DEV float ld_g1(const uint16_t* g, long i) { return h2f(g[i]); }
-PSX_DEV void ld_g4(const float* g, long i, float (&v)[4]) {
-  const f32x4 t = *reinterpret_cast<const f32x4*>(g + i);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = t[j];
-}
-PSX_DEV void ld_g4(const uint16_t* g, long i, float (&v)[4]) {
-  const u32x2 t = *reinterpret_cast<const u32x2*>(g + i);
-  v[0] = h2f(t[0] & 0xffff);
-  v[1] = h2f(t[0] >> 16);
-  v[2] = h2f(t[1] & 0xffff);
-  v[3] = h2f(t[1] >> 16);
-}
+// body: int8 q[n], padded to a multiple of 16 bytes
+static inline BlockLayout q8_layout(long n) { return block_layout(n, (n + 15) & ~15L); }
 
 // int8 number j (0..3) of a packed word, as float
 PSX_DEV float q8_f(uint32_t w, int j) { return (float)((int)(w << (24 - 8 * j)) >> 24); }
@@ -98,221 +72,138 @@ PSX_DEV void q8_quant4(const float (&v)[4], float& scale, uint32_t& w, float (&d
   }
 }
 
-// Blocks [blk0, blk1) of the arena. VEC: g, resid 16-byte (fp16 g: 8-byte) aligned; the tail
+// What an encode quantises and what it leaves behind, per element: `ro` is the array it only
+// reads, `rw` the fp32 one it reads and writes back.
+struct Q8Push {  // the push wire: the block is resid + g, and resid keeps block - deq
+  PSX_DEV static float block(float rw, float ro) { return rw + ro; }
+  PSX_DEV static float back(float, float blk, float deq) { return blk - deq; }
+};
+struct Q8Fetch {  // the fetch wire: the block is arena - shadow, and shadow becomes shadow + deq
+  PSX_DEV static float block(float rw, float ro) { return ro - rw; }
+  PSX_DEV static float back(float rw, float, float deq) { return rw + deq; }
+};
+
+// Blocks [blk0, blk1) of the arena. VEC: ro, rw 16-byte (fp16 ro: 8-byte) aligned; the tail
 // block (the one holding element n - 1 when n % 256 != 0) and the unaligned form go element by
-// element and touch nothing at or past n in g or resid. q words past n within the padded section
+// element and touch nothing at or past n in ro or rw. q words past n within the padded section
 // [0, qwords) are written as zeros.
+template <typename P, typename GT, bool VEC>
+PSX_DEV void q8_encode_blocks(const GT* __restrict__ ro, float* __restrict__ rw, long n, long blk0, long blk1,
+                              float* __restrict__ scales, uint32_t* __restrict__ qw, long qwords,
+                              int* __restrict__ hdr) {
+  const int lane = threadIdx.x & 63;
+  block_write_header(hdr, kQ8Magic, n);
+  const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
+  for (long b = blk0 + wave; b < blk1; b += nwaves) {
+    const long e = b * kBlock + lane * 4;
+    const bool full = (b + 1) * kBlock <= n;  // wave-uniform
+    float old[4], blk[4];
+    if (VEC && full) {
+      float rv[4];
+      ld_g4(ro, e, rv);
+      const f32x4 t = *reinterpret_cast<const f32x4*>(rw + e);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        old[j] = t[j];
+        blk[j] = P::block(t[j], rv[j]);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        old[j] = e + j < n ? rw[e + j] : 0.f;
+        blk[j] = e + j < n ? P::block(old[j], ld_g1(ro, e + j)) : 0.f;
+      }
+    }
+    uint32_t w;
+    float scale, deq[4], out[4];
+    q8_quant4(blk, scale, w, deq);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[j] = P::back(old[j], blk[j], deq[j]);
+    if (VEC && full) {
+      *reinterpret_cast<f32x4*>(rw + e) = (f32x4){out[0], out[1], out[2], out[3]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (e + j < n) rw[e + j] = out[j];
+    }
+    if ((e >> 2) < qwords) qw[e >> 2] = w;
+    if (lane == 0) scales[b] = scale;
+  }
+}
+
 template <typename GT, bool VEC>
 __global__ __launch_bounds__(256) void q8_encode_kernel(const GT* __restrict__ g, float* __restrict__ resid, long n,
                                                         long blk0, long blk1, float* __restrict__ scales,
                                                         uint32_t* __restrict__ qw, long qwords,
                                                         int* __restrict__ hdr) {
-  const int lane = threadIdx.x & 63;
-  if (hdr != nullptr && blockIdx.x == 0 && threadIdx.x < 4) {
-    const long nblk = (n + kQ8Block - 1) / kQ8Block;
-    hdr[threadIdx.x] = threadIdx.x == 0 ? kQ8Magic : threadIdx.x == 1 ? (int)n : threadIdx.x == 2 ? kQ8Block : (int)nblk;
-  }
-  const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
-  for (long b = blk0 + wave; b < blk1; b += nwaves) {
-    const long e = b * kQ8Block + lane * 4;
-    const bool full = (b + 1) * kQ8Block <= n;  // wave-uniform
-    float acc[4];
-    if (VEC && full) {
-      float gv[4];
-      ld_g4(g, e, gv);
-      const f32x4 r = *reinterpret_cast<const f32x4*>(resid + e);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = r[j] + gv[j];
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = e + j < n ? resid[e + j] + ld_g1(g, e + j) : 0.f;
-    }
-    uint32_t w;
-    float scale, deq[4], res[4];
-    q8_quant4(acc, scale, w, deq);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) res[j] = acc[j] - deq[j];
-    if (VEC && full) {
-      *reinterpret_cast<f32x4*>(resid + e) = (f32x4){res[0], res[1], res[2], res[3]};
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (e + j < n) resid[e + j] = res[j];
-    }
-    if ((e >> 2) < qwords) qw[e >> 2] = w;
-    if (lane == 0) scales[b] = scale;
-  }
+  q8_encode_blocks<Q8Push, GT, VEC>(g, resid, n, blk0, blk1, scales, qw, qwords, hdr);
 }
 
-// The fetch wire's encode (--fetch-codec q8delta, parallel/fetchq8.py): the same pass with
-// d = arena - shadow in place of resid + g, and shadow = shadow + deq (the copy every worker
-// holds) in place of the residual. Same forms, same bounds: nothing at or past n is touched in
-// arena or shadow. 13 bytes per element: 8 read, 4 + 1 written.
+// The fetch wire's encode (--fetch-codec q8delta, parallel/fetchq8.py): the same pass over
+// arena and shadow. 13 bytes per element: 8 read, 4 + 1 written.
 template <bool VEC>
 __global__ __launch_bounds__(256) void fetchq8_encode_kernel(const float* __restrict__ arena,
                                                              float* __restrict__ shadow, long n, long blk0, long blk1,
                                                              float* __restrict__ scales, uint32_t* __restrict__ qw,
                                                              long qwords, int* __restrict__ hdr) {
-  const int lane = threadIdx.x & 63;
-  if (hdr != nullptr && blockIdx.x == 0 && threadIdx.x < 4) {
-    const long nblk = (n + kQ8Block - 1) / kQ8Block;
-    hdr[threadIdx.x] = threadIdx.x == 0 ? kQ8Magic : threadIdx.x == 1 ? (int)n : threadIdx.x == 2 ? kQ8Block : (int)nblk;
-  }
-  const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
-  for (long b = blk0 + wave; b < blk1; b += nwaves) {
-    const long e = b * kQ8Block + lane * 4;
-    const bool full = (b + 1) * kQ8Block <= n;  // wave-uniform
-    float sh[4], d[4];
-    if (VEC && full) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(arena + e);
-      const f32x4 s = *reinterpret_cast<const f32x4*>(shadow + e);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        sh[j] = s[j];
-        d[j] = a[j] - s[j];
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        sh[j] = e + j < n ? shadow[e + j] : 0.f;
-        d[j] = e + j < n ? arena[e + j] - sh[j] : 0.f;
-      }
-    }
-    uint32_t w;
-    float scale, deq[4];
-    q8_quant4(d, scale, w, deq);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sh[j] = sh[j] + deq[j];
-    if (VEC && full) {
-      *reinterpret_cast<f32x4*>(shadow + e) = (f32x4){sh[0], sh[1], sh[2], sh[3]};
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (e + j < n) shadow[e + j] = sh[j];
-    }
-    if ((e >> 2) < qwords) qw[e >> 2] = w;
-    if (lane == 0) scales[b] = scale;
-  }
+  q8_encode_blocks<Q8Fetch, float, VEC>(arena, shadow, n, blk0, blk1, scales, qw, qwords, hdr);
 }
 
-struct Q8Srcs {
-  const uint8_t* p[kMaxSrc];
-  int n;
+// The codec policy of the shared update forms (blockwire.hpp). The rows form takes q as one dword
+// per row and source and the row's scale, wave-uniform, and issues two sources' loads ahead of
+// their first use. The form with one 16-byte q load per lane (a lane owning 16 consecutive
+// elements) makes each of its four p loads touch a quarter of 64 separate 64-byte segments; it
+// measured 21.7 us against 16.2 us for this one (W = 1, n = 11.2 M; the fp16-wire kernel: 17.5 us).
+struct Q8Wire {
+  PSX_DEV static float deq1(const uint8_t* payload, long q_off, long i) {
+    const float sc = reinterpret_cast<const float*>(payload + 16)[i / kBlock];
+    const float qf = (float)reinterpret_cast<const int8_t*>(payload + q_off)[i];
+    return qf * sc;
+  }
+  PSX_DEV static long unit_base(long e0, long u) { return e0 + (u << 10); }
+  static constexpr int kAhead = 2;
+  struct Unit {
+    uint32_t qv[4];
+    float sc[4];
+  };
+  PSX_DEV static void load(const uint8_t* payload, long q_off, long ub, int lane, Unit& un) {
+    const long e = ub + lane * 4;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      un.qv[v] = *reinterpret_cast<const uint32_t*>(payload + q_off + e + 256 * v);
+      un.sc[v] = reinterpret_cast<const float*>(payload + 16)[(e >> 8) + v];
+    }
+  }
+  PSX_DEV static void add(const Unit& un, float (&s)[16]) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) s[j] = s[j] + q8_f(un.qv[j >> 2], j & 3) * un.sc[j >> 2];
+  }
 };
-
-// one element's decoded sum over the sources, in source order
-PSX_DEV float q8_sum1(const Q8Srcs& srcs, long q_off, long i) {
-  float s = 0.f;
-  for (int k = 0; k < srcs.n; ++k) {
-    const float sc = reinterpret_cast<const float*>(srcs.p[k] + 16)[i / kQ8Block];
-    const float qf = (float)reinterpret_cast<const int8_t*>(srcs.p[k] + q_off)[i];
-    s = s + qf * sc;
-  }
-  return s;
-}
 
 // Elements [e0, e1) (e0 a multiple of 256). Element-wise form: any alignment.
 template <bool MOM>
-__global__ __launch_bounds__(256) void q8_apply_multi_kernel(float* __restrict__ p, Q8Srcs srcs, long q_off,
+__global__ __launch_bounds__(256) void q8_apply_multi_kernel(float* __restrict__ p, BlockSrcs srcs, long q_off,
                                                              float* __restrict__ buf, long e0, long e1, float lr,
                                                              float gscale, float momentum, float wd, int first,
                                                              uint16_t* __restrict__ img) {
-  for (long i = e0 + blockIdx.x * (long)blockDim.x + threadIdx.x; i < e1; i += (long)gridDim.x * blockDim.x) {
-    const float pv = p[i];
-    const float nv = sgd_tail<MOM>(q8_sum1(srcs, q_off, i), pv, buf + i, lr, gscale, momentum, wd, first);
-    p[i] = nv;
-    if (img) img[i] = f2bf(nv);
-  }
+  block_apply_elems<MOM, Q8Wire>(p, srcs, q_off, buf, e0 + blockIdx.x * (long)blockDim.x + threadIdx.x,
+                                 (long)gridDim.x * blockDim.x, e1, lr, gscale, momentum, wd, first, img, img != nullptr);
 }
 
-// Vectorised form: a wave covers 1024 elements as 4 rows of 256 (one block each); lane l owns
-// elements 4 l .. 4 l + 3 of every row, 16 int8 per lane per source. Every p / buf access is
-// 16 bytes per lane and contiguous across the wave, q is one dword per row and source, the
-// row's scale is wave-uniform, and a lane's loads are issued ahead of their first use (p and buf
-// first, then the sources two at a time). The form with one 16-byte q load per lane (a lane
-// owning 16 consecutive elements) makes each of its four p loads touch a quarter of 64 separate
-// 64-byte segments; it measured 21.7 us against 16.2 us for this one (W = 1, n = 11.2 M; the
-// fp16-wire kernel: 17.5 us). p, buf, img 16-byte aligned; what is left of the range after the
-// whole 1024-element units goes element by element in workgroup 0.
+// Vectorised form (blockwire.hpp block_apply_rows): p, buf, img 16-byte aligned.
 template <bool MOM, bool IMG>
-__global__ __launch_bounds__(256) void q8_apply_multi_rows_kernel(float* __restrict__ p, Q8Srcs srcs, long q_off,
+__global__ __launch_bounds__(256) void q8_apply_multi_rows_kernel(float* __restrict__ p, BlockSrcs srcs, long q_off,
                                                                   float* __restrict__ buf, long e0, long e1, float lr,
                                                                   float gscale, float momentum, float wd, int first,
                                                                   uint16_t* __restrict__ img) {
-  const long nu = (e1 - e0) >> 10;  // whole 1024-element units
-  const long t0 = e0 + (nu << 10);
-  if (blockIdx.x == 0) {
-    for (long i = t0 + threadIdx.x; i < e1; i += blockDim.x) {
-      const float pv = p[i];
-      const float nv = sgd_tail<MOM>(q8_sum1(srcs, q_off, i), pv, buf + i, lr, gscale, momentum, wd, first);
-      p[i] = nv;
-      if (IMG) img[i] = f2bf(nv);
-    }
-  }
-  const int lane = threadIdx.x & 63;
-  const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
-  for (long u = wave; u < nu; u += nwaves) {
-    const long e = e0 + (u << 10) + lane * 4;  // row v: e + 256 v
-    f32x4 pv[4];
-    float bv[16] = {};
-#pragma unroll
-    for (int v = 0; v < 4; ++v) pv[v] = *reinterpret_cast<const f32x4*>(p + e + 256 * v);
-    if (MOM && !first) {
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(buf + e + 256 * v);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bv[4 * v + j] = t[j];
-      }
-    }
-    float s[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) s[j] = 0.f;
-    for (int k0 = 0; k0 < srcs.n; k0 += 2) {
-      uint32_t qv[2][4];
-      float sc[2][4];
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-        if (k0 + m < srcs.n) {
-          const uint8_t* base = srcs.p[k0 + m];
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            qv[m][v] = *reinterpret_cast<const uint32_t*>(base + q_off + e + 256 * v);
-            sc[m][v] = reinterpret_cast<const float*>(base + 16)[(e >> 8) + v];
-          }
-        }
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-        if (k0 + m < srcs.n) {
-#pragma unroll
-          for (int j = 0; j < 16; ++j) s[j] = s[j] + q8_f(qv[m][j >> 2], j & 3) * sc[m][j >> 2];
-        }
-    }
-#pragma unroll
-    for (int v = 0; v < 4; ++v)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        pv[v][j] = sgd_tail<MOM>(s[4 * v + j], pv[v][j], &bv[4 * v + j], lr, gscale, momentum, wd, first);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) *reinterpret_cast<f32x4*>(p + e + 256 * v) = pv[v];
-    if (MOM) {
-#pragma unroll
-      for (int v = 0; v < 4; ++v)
-        *reinterpret_cast<f32x4*>(buf + e + 256 * v) = (f32x4){bv[4 * v], bv[4 * v + 1], bv[4 * v + 2], bv[4 * v + 3]};
-    }
-    if (IMG) {
-#pragma unroll
-      for (int v = 0; v < 4; ++v)
-        *reinterpret_cast<u32x2*>(img + e + 256 * v) = (u32x2){pack_bf2(pv[v][0], pv[v][1]), pack_bf2(pv[v][2], pv[v][3])};
-    }
-  }
+  block_apply_rows<MOM, IMG, Q8Wire>(p, srcs, q_off, buf, e0, e1, lr, gscale, momentum, wd, first, img, blockDim.x);
 }
 
 // dst[i] = [dst[i] +] scale * (float(q[i]) * scales[i / 256]) over [e0, e1); VEC: dst 16-byte
 // aligned, 16 elements per lane, the e1 % 16 tail element by element in workgroup 0.
 template <bool ADD>
 PSX_DEV void q8_dec1(const float* scales, const int8_t* q, float* dst, long i, float scale) {
-  const float v = scale * ((float)q[i] * scales[i / kQ8Block]);
+  const float v = scale * ((float)q[i] * scales[i / kBlock]);
   dst[i] = ADD ? dst[i] + v : v;
 }
 
@@ -348,10 +239,26 @@ __global__ __launch_bounds__(256) void q8_decode_kernel(const float* __restrict_
 
 using namespace psx;
 
-// [off, off + cnt) must start on a block and end on a block or at n
-static bool q8_range_ok(long n, long off, long cnt) {
-  return n > 0 && n <= 0x7fffffffL && off >= 0 && cnt >= 0 && off % kQ8Block == 0 && off + cnt <= n &&
-         ((off + cnt) % kQ8Block == 0 || off + cnt == n);
+// What the two encodes hand their kernels: the sections of `payload` and the blocks of the range.
+struct Q8EncodeArgs {
+  float* scales;
+  uint32_t* qw;
+  long qwords, blk0, blk1;
+  int* hdr;  // written by the call that covers block 0
+  dim3 grid;
+};
+static bool q8_encode_args(long n, void* payload, long off, long cnt, Q8EncodeArgs& a) {
+  if (!block_range_ok(n, off, cnt) || !al16(payload)) return false;
+  const BlockLayout l = q8_layout(n);
+  uint8_t* pl = (uint8_t*)payload;
+  a.scales = (float*)(pl + l.scales_off);
+  a.qw = (uint32_t*)(pl + l.body_off);
+  a.qwords = (l.bytes - l.body_off) / 4;
+  a.blk0 = off / kBlock;
+  a.blk1 = (off + cnt + kBlock - 1) / kBlock;
+  a.hdr = off == 0 ? (int*)pl : nullptr;
+  a.grid = dim3(stream_grid((a.blk1 - a.blk0) * 64));
+  return true;
 }
 
 extern "C" {
@@ -363,25 +270,14 @@ long psx_q8_payload_bytes(long n) { return q8_layout(n).bytes; }
 // fp32 or fp16 (g_fp16). The header is written by the call that covers block 0.
 int psx_q8_encode(const void* g, int g_fp16, float* resid, long n, void* payload, long off, long cnt,
                   hipStream_t st) {
-  if (!q8_range_ok(n, off, cnt) || (uintptr_t)payload % 16 != 0) return (int)hipErrorInvalidValue;
+  Q8EncodeArgs a;
+  if (!q8_encode_args(n, payload, off, cnt, a)) return (int)hipErrorInvalidValue;
   if (cnt == 0) return 0;
-  const Q8Layout l = q8_layout(n);
-  uint8_t* pl = (uint8_t*)payload;
-  float* scales = (float*)(pl + l.scales_off);
-  uint32_t* qw = (uint32_t*)(pl + l.q_off);
-  const long qwords = (l.bytes - l.q_off) / 4;
-  const long blk0 = off / kQ8Block, blk1 = (off + cnt + kQ8Block - 1) / kQ8Block;
-  int* hdr = off == 0 ? (int*)pl : nullptr;
-  const bool vec = (uintptr_t)resid % 16 == 0 && (uintptr_t)g % (g_fp16 ? 8 : 16) == 0;
-  const dim3 grid(stream_grid((blk1 - blk0) * 64));
-#define PSX_Q8E(G, V)                                                                                            \
-  hipLaunchKernelGGL((q8_encode_kernel<G, V>), grid, dim3(256), 0, st, (const G*)g, resid, n, blk0, blk1, scales, \
-                     qw, qwords, hdr)
-  if (g_fp16 && vec) PSX_Q8E(uint16_t, true);
-  else if (g_fp16) PSX_Q8E(uint16_t, false);
-  else if (vec) PSX_Q8E(float, true);
-  else PSX_Q8E(float, false);
-#undef PSX_Q8E
+  const bool vec = al16(resid) && (uintptr_t)g % (g_fp16 ? 8 : 16) == 0;
+  dispatch2(g_fp16 != 0, vec, [&](auto fp16, auto v) {
+    hipLaunchKernelGGL((q8_encode_kernel<wire_t<decltype(fp16)>, decltype(v)::value>), a.grid, dim3(256), 0, st,
+                       (const wire_t<decltype(fp16)>*)g, resid, n, a.blk0, a.blk1, a.scales, a.qw, a.qwords, a.hdr);
+  });
   return (int)hipGetLastError();
 }
 
@@ -390,85 +286,67 @@ int psx_q8_encode(const void* g, int g_fp16, float* resid, long n, void* payload
 // arrays. The header is written by the call that covers block 0.
 int psx_fetchq8_encode(const float* arena, float* shadow, long n, void* payload, long off, long cnt,
                        hipStream_t st) {
-  if (!q8_range_ok(n, off, cnt) || (uintptr_t)payload % 16 != 0) return (int)hipErrorInvalidValue;
+  Q8EncodeArgs a;
+  if (!q8_encode_args(n, payload, off, cnt, a)) return (int)hipErrorInvalidValue;
   if (cnt == 0) return 0;
-  const Q8Layout l = q8_layout(n);
-  uint8_t* pl = (uint8_t*)payload;
-  float* scales = (float*)(pl + l.scales_off);
-  uint32_t* qw = (uint32_t*)(pl + l.q_off);
-  const long qwords = (l.bytes - l.q_off) / 4;
-  const long blk0 = off / kQ8Block, blk1 = (off + cnt + kQ8Block - 1) / kQ8Block;
-  int* hdr = off == 0 ? (int*)pl : nullptr;
-  const dim3 grid(stream_grid((blk1 - blk0) * 64));
-  if ((uintptr_t)arena % 16 == 0 && (uintptr_t)shadow % 16 == 0)
-    hipLaunchKernelGGL(fetchq8_encode_kernel<true>, grid, dim3(256), 0, st, arena, shadow, n, blk0, blk1, scales, qw,
-                       qwords, hdr);
+  if (al16(arena) && al16(shadow))
+    hipLaunchKernelGGL(fetchq8_encode_kernel<true>, a.grid, dim3(256), 0, st, arena, shadow, n, a.blk0, a.blk1,
+                       a.scales, a.qw, a.qwords, a.hdr);
   else
-    hipLaunchKernelGGL(fetchq8_encode_kernel<false>, grid, dim3(256), 0, st, arena, shadow, n, blk0, blk1, scales, qw,
-                       qwords, hdr);
+    hipLaunchKernelGGL(fetchq8_encode_kernel<false>, a.grid, dim3(256), 0, st, arena, shadow, n, a.blk0, a.blk1,
+                       a.scales, a.qw, a.qwords, a.hdr);
   return (int)hipGetLastError();
 }
 
 // p[off:off+cnt] -= lr * (gscale * sum_k deq_k [+ wd p]) [momentum] straight from nsrc <= 32
 // payloads (host array of device pointers, each the whole arena's payload), decoded and summed
 // in fp32 in source order; img (optional): bf16 image of the updated parameters. p, buf, img:
-// element 0 of the n-element arrays.
+// element 0 of the n-element arrays. A payload may share no byte with p, buf or img.
 int psx_q8_apply_multi(float* p, const void* const* payloads, int nsrc, float* buf, long n, long off, long cnt,
                        float lr, float gscale, float momentum, float wd, int first, void* img, hipStream_t st) {
-  if (nsrc < 1 || nsrc > kMaxSrc || !q8_range_ok(n, off, cnt)) return (int)hipErrorInvalidValue;
-  if (cnt == 0) return 0;
-  const Q8Layout l = q8_layout(n);
-  Q8Srcs sl{};
-  sl.n = nsrc;
-  bool aligned = (uintptr_t)p % 16 == 0 && (uintptr_t)buf % 16 == 0 && (uintptr_t)img % 16 == 0;
-  for (int k = 0; k < nsrc; ++k) {
-    sl.p[k] = (const uint8_t*)payloads[k];
-    if ((uintptr_t)payloads[k] % 16 != 0) return (int)hipErrorInvalidValue;
-  }
+  const BlockLayout l = q8_layout(n);
+  BlockSrcs sl{};
+  if (const int e = block_apply_prologue(payloads, nsrc, l.bytes, n, off, cnt, p, buf, img, sl); e != 0 || sl.n == 0)
+    return e;
   const bool mom = buf != nullptr && momentum != 0.f;
   uint16_t* im = (uint16_t*)img;
   const long e0 = off, e1 = off + cnt;
-  if (aligned && cnt >= 1024) {
+  if (al16(p) && al16(buf) && al16(img) && cnt >= 1024) {
     const dim3 grid(stream_grid((cnt >> 10) * 64));
-#define PSX_Q8A(M, I)                                                                                            \
-  hipLaunchKernelGGL((q8_apply_multi_rows_kernel<M, I>), grid, dim3(256), 0, st, p, sl, l.q_off, buf, e0, e1, lr, \
-                     gscale, momentum, wd, first, im)
-    if (mom && im) PSX_Q8A(true, true);
-    else if (mom) PSX_Q8A(true, false);
-    else if (im) PSX_Q8A(false, true);
-    else PSX_Q8A(false, false);
-#undef PSX_Q8A
+    dispatch2(mom, im != nullptr, [&](auto m, auto i) {
+      hipLaunchKernelGGL((q8_apply_multi_rows_kernel<decltype(m)::value, decltype(i)::value>), grid, dim3(256), 0, st,
+                         p, sl, l.body_off, buf, e0, e1, lr, gscale, momentum, wd, first, im);
+    });
     return (int)hipGetLastError();
   }
   const dim3 grid(stream_grid(cnt));
   if (mom)
-    hipLaunchKernelGGL(q8_apply_multi_kernel<true>, grid, dim3(256), 0, st, p, sl, l.q_off, buf, e0, e1, lr, gscale,
+    hipLaunchKernelGGL(q8_apply_multi_kernel<true>, grid, dim3(256), 0, st, p, sl, l.body_off, buf, e0, e1, lr, gscale,
                        momentum, wd, first, im);
   else
-    hipLaunchKernelGGL(q8_apply_multi_kernel<false>, grid, dim3(256), 0, st, p, sl, l.q_off, buf, e0, e1, lr, gscale,
-                       momentum, wd, first, im);
+    hipLaunchKernelGGL(q8_apply_multi_kernel<false>, grid, dim3(256), 0, st, p, sl, l.body_off, buf, e0, e1, lr,
+                       gscale, momentum, wd, first, im);
   return (int)hipGetLastError();
 }
 
-// dst[off:off+cnt] = [dst +] scale * deq (dst: element 0 of the n-element fp32 array).
+// dst[off:off+cnt] = [dst +] scale * deq (dst: element 0 of the n-element fp32 array, sharing no
+// byte with the payload).
 int psx_q8_decode(const void* payload, float* dst, long n, long off, long cnt, float scale, int add,
                   hipStream_t st) {
-  if (!q8_range_ok(n, off, cnt) || (uintptr_t)payload % 16 != 0) return (int)hipErrorInvalidValue;
+  if (!block_range_ok(n, off, cnt) || !al16(payload)) return (int)hipErrorInvalidValue;
   if (cnt == 0) return 0;
-  const Q8Layout l = q8_layout(n);
+  const BlockLayout l = q8_layout(n);
+  if (ranges_overlap(payload, (size_t)l.bytes, dst, (size_t)n * 4)) return (int)hipErrorInvalidValue;
   const uint8_t* pl = (const uint8_t*)payload;
   const float* scales = (const float*)(pl + l.scales_off);
-  const int8_t* q = (const int8_t*)(pl + l.q_off);
+  const int8_t* q = (const int8_t*)(pl + l.body_off);
   const long e0 = off, e1 = off + cnt;
-  const bool vec = (uintptr_t)dst % 16 == 0 && cnt >= 16;
+  const bool vec = al16(dst) && cnt >= 16;
   const dim3 grid(stream_grid(vec ? cnt / 16 : cnt));
-#define PSX_Q8D(A, V) \
-  hipLaunchKernelGGL((q8_decode_kernel<A, V>), grid, dim3(256), 0, st, scales, q, dst, e0, e1, scale)
-  if (add && vec) PSX_Q8D(true, true);
-  else if (add) PSX_Q8D(true, false);
-  else if (vec) PSX_Q8D(false, true);
-  else PSX_Q8D(false, false);
-#undef PSX_Q8D
+  dispatch2(add != 0, vec, [&](auto a, auto v) {
+    hipLaunchKernelGGL((q8_decode_kernel<decltype(a)::value, decltype(v)::value>), grid, dim3(256), 0, st, scales, q,
+                       dst, e0, e1, scale);
+  });
   return (int)hipGetLastError();
 }
 

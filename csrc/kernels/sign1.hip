@@ -6,6 +6,8 @@
 //   | signs:  uint64[4 * nblk]   (32 bytes per block) ]
 // Blocks are runs of 256 consecutive elements of the flat parameter arena and are independent:
 // every entry point takes a 256-aligned element sub-range [off, off + cnt).
+// The frame (layout, range check, gradient loaders, header write, the source list and the two
+// forms of the update from payloads) is blockwire.hpp's; here is the codec's arithmetic.
 // Word j (0..3) of a block has bit l (0..63) equal to the sign of block element 4 l + j: the lane
 // that owns elements 4 l .. 4 l + 3 contributes bit l to each of four ballots, and a word read
 // back is the lane mask of its row of elements.
@@ -29,9 +31,7 @@
 //                         (sgd_tail.hpp)
 //   * sign1_decode      : dst = [dst +] scale * deq (every other rule, in-process accumulation,
 //                         reference semantics)
-#include <float.h>
-
-#include "wire.hpp"
+#include "blockwire.hpp"
 
 // Everything below keeps its multiplies and adds apart (hipcc contracts by default); the shared
 // update tail above was parsed with the library default, as in optim.hip.
@@ -39,20 +39,10 @@
 
 namespace psx {
 
-constexpr int kS1Block = 256;
 constexpr int kS1Magic = 0x31423153;  // the bytes 'S' '1' 'B' '1'
 
-struct S1Layout {
-  long nblk, scales_off, w_off, bytes;
-};
-static inline S1Layout s1_layout(long n) {
-  S1Layout l;
-  l.nblk = (n + kS1Block - 1) / kS1Block;
-  l.scales_off = 16;
-  l.w_off = l.scales_off + ((4 * l.nblk + 15) & ~15L);
-  l.bytes = l.w_off + 32 * l.nblk;
-  return l;
-}
+// body: uint64 signs[4 * nblk] (32 bytes per block)
+static inline BlockLayout s1_layout(long n) { return block_layout(n, 32 * block_count(n)); }
 
 // A payload is only read by the kernels that take one, so its scales and sign words are loaded
 // through the constant address space: with a wave-uniform address such a load is a scalar load.
@@ -60,22 +50,6 @@ typedef const __attribute__((address_space(4))) float* s1_cf32;
 typedef const __attribute__((address_space(4))) uint64_t* s1_cu64;
 PSX_DEV s1_cf32 s1_scales(const uint8_t* payload) { return (s1_cf32)(uintptr_t)(payload + 16); }
 PSX_DEV s1_cu64 s1_words(const uint8_t* payload, long w_off) { return (s1_cu64)(uintptr_t)(payload + w_off); }
-
-PSX_DEV float s1_h2f(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (uint16_t)bits); }
-PSX_DEV float s1_ld_g1(const float* g, long i) { return g[i]; }
-PSX_DEV float s1_ld_g1(const uint16_t* g, long i) { return s1_h2f(g[i]); }
-PSX_DEV void s1_ld_g4(const float* g, long i, float (&v)[4]) {
-  const f32x4 t = *reinterpret_cast<const f32x4*>(g + i);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = t[j];
-}
-PSX_DEV void s1_ld_g4(const uint16_t* g, long i, float (&v)[4]) {
-  const u32x2 t = *reinterpret_cast<const u32x2*>(g + i);
-  v[0] = s1_h2f(t[0] & 0xffff);
-  v[1] = s1_h2f(t[0] >> 16);
-  v[2] = s1_h2f(t[1] & 0xffff);
-  v[3] = s1_h2f(t[1] >> 16);
-}
 
 // this lane's bit of a sign word that is the same in every lane (bit l belongs to lane l: the
 // word is a lane mask, and the select on it takes the scalar pair as its condition)
@@ -90,24 +64,21 @@ __global__ __launch_bounds__(256) void sign1_encode_kernel(const GT* __restrict_
                                                            long n, long blk0, long blk1, float* __restrict__ scales,
                                                            uint64_t* __restrict__ words, int* __restrict__ hdr) {
   const int lane = threadIdx.x & 63;
-  if (hdr != nullptr && blockIdx.x == 0 && threadIdx.x < 4) {
-    const long nblk = (n + kS1Block - 1) / kS1Block;
-    hdr[threadIdx.x] = threadIdx.x == 0 ? kS1Magic : threadIdx.x == 1 ? (int)n : threadIdx.x == 2 ? kS1Block : (int)nblk;
-  }
+  block_write_header(hdr, kS1Magic, n);
   const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
   for (long b = blk0 + wave; b < blk1; b += nwaves) {
-    const long e = b * kS1Block + lane * 4;
-    const bool full = (b + 1) * kS1Block <= n;  // wave-uniform
+    const long e = b * kBlock + lane * 4;
+    const bool full = (b + 1) * kBlock <= n;  // wave-uniform
     float acc[4];
     if (VEC && full) {
       float gv[4];
-      s1_ld_g4(g, e, gv);
+      ld_g4(g, e, gv);
       const f32x4 r = *reinterpret_cast<const f32x4*>(resid + e);
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[j] = r[j] + gv[j];
     } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = e + j < n ? resid[e + j] + s1_ld_g1(g, e + j) : 0.f;
+      for (int j = 0; j < 4; ++j) acc[j] = e + j < n ? resid[e + j] + ld_g1(g, e + j) : 0.f;
     }
     float a[4];
     bool bad = false;
@@ -118,7 +89,7 @@ __global__ __launch_bounds__(256) void sign1_encode_kernel(const GT* __restrict_
     }
     const float sum = wave_sum(((a[0] + a[1]) + a[2]) + a[3]);
     const bool blk_bad = __ballot(bad) != 0ull;
-    const float cnt = full ? (float)kS1Block : (float)(n - b * kS1Block);
+    const float cnt = full ? (float)kBlock : (float)(n - b * kBlock);
     const float scale = blk_bad ? __builtin_nanf("") : sum / cnt;
     unsigned long long w[4];
     float res[4];
@@ -140,120 +111,64 @@ __global__ __launch_bounds__(256) void sign1_encode_kernel(const GT* __restrict_
   }
 }
 
-struct S1Srcs {
-  const uint8_t* p[kMaxSrc];
-  int n;
+// The codec policy of the shared update forms (blockwire.hpp). Of a source the wave needs its
+// unit's 4 scales and 16 sign words, 144 contiguous-by-section bytes at wave-uniform addresses (the
+// block index goes through readfirstlane, the pointers are to constant memory): scalar loads,
+// which leave the vector memory path to p, buf and img. Word 4 v + j is the lane mask of element j
+// of row v: the decode of an element is one select between scale and -scale. What a further
+// source costs follows the number of scalar load requests (three per source and unit here: the
+// scales, two times eight words), not their bytes and not their latency: units of 512 or 256
+// elements (four and eight requests per 1024 elements) measured 63 and 96 us against 51 us at
+// W = 32, n = 11.2 M, and issuing two or four sources' loads together before the first use
+// changed nothing (profiles/sign1_kernels.txt).
+struct S1Wire {
+  PSX_DEV static float deq1(const uint8_t* payload, long w_off, long i) {
+    const long b = i / kBlock;
+    const int r = (int)(i - b * kBlock);
+    const uint64_t w = reinterpret_cast<const uint64_t*>(payload + w_off)[4 * b + (r & 3)];
+    return s1_deq((w >> (r >> 2)) & 1, reinterpret_cast<const float*>(payload + 16)[b]);
+  }
+  // the unit's first block is below 2^23 (n < 2^31) and the same in every lane
+  PSX_DEV static long unit_base(long e0, long u) {
+    return (long)__builtin_amdgcn_readfirstlane((int)((e0 >> 8) + (u << 2))) * kBlock;
+  }
+  static constexpr int kAhead = 1;
+  struct Unit {
+    float sc[4];
+    uint64_t w[16];
+  };
+  PSX_DEV static void load(const uint8_t* payload, long w_off, long ub, int, Unit& un) {
+    const int b = (int)(ub >> 8);
+    const s1_cf32 scp = s1_scales(payload) + b;
+    const s1_cu64 wp = s1_words(payload, w_off) + 4 * (long)b;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) un.sc[v] = scp[v];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) un.w[j] = wp[j];
+  }
+  PSX_DEV static void add(const Unit& un, float (&s)[16]) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) s[j] = s[j] + s1_deq(s1_lane_bit(un.w[j]), un.sc[j >> 2]);
+  }
 };
-
-// element i of one payload, decoded
-PSX_DEV float s1_deq1(const uint8_t* payload, long w_off, long i) {
-  const long b = i / kS1Block;
-  const int r = (int)(i - b * kS1Block);
-  const uint64_t w = reinterpret_cast<const uint64_t*>(payload + w_off)[4 * b + (r & 3)];
-  return s1_deq((w >> (r >> 2)) & 1, reinterpret_cast<const float*>(payload + 16)[b]);
-}
-
-// one element's decoded sum over the sources, in source order
-PSX_DEV float s1_sum1(const S1Srcs& srcs, long w_off, long i) {
-  float s = 0.f;
-  for (int k = 0; k < srcs.n; ++k) s = s + s1_deq1(srcs.p[k], w_off, i);
-  return s;
-}
 
 // Elements [e0, e1) (e0 a multiple of 256). Element-wise form: any alignment.
 template <bool MOM>
-__global__ __launch_bounds__(256) void sign1_apply_multi_kernel(float* __restrict__ p, S1Srcs srcs, long w_off,
+__global__ __launch_bounds__(256) void sign1_apply_multi_kernel(float* __restrict__ p, BlockSrcs srcs, long w_off,
                                                                 float* __restrict__ buf, long e0, long e1, float lr,
                                                                 float gscale, float momentum, float wd, int first,
                                                                 uint16_t* __restrict__ img) {
-  for (long i = e0 + blockIdx.x * (long)blockDim.x + threadIdx.x; i < e1; i += (long)gridDim.x * blockDim.x) {
-    const float pv = p[i];
-    const float nv = sgd_tail<MOM>(s1_sum1(srcs, w_off, i), pv, buf + i, lr, gscale, momentum, wd, first);
-    p[i] = nv;
-    if (img) img[i] = f2bf(nv);
-  }
+  block_apply_elems<MOM, S1Wire>(p, srcs, w_off, buf, e0 + blockIdx.x * (long)blockDim.x + threadIdx.x,
+                                 (long)gridDim.x * blockDim.x, e1, lr, gscale, momentum, wd, first, img, img != nullptr);
 }
 
-// Vectorised form: a wave covers 1024 elements as 4 rows of 256 (one block each); lane l owns
-// elements 4 l .. 4 l + 3 of every row, so every p / buf / img access is 16 bytes per lane and
-// contiguous across the wave. Of a source the wave needs the rows' 4 scales and 16 sign words,
-// 144 contiguous-by-section bytes at wave-uniform addresses (the block index goes through
-// readfirstlane, the pointers are to constant memory): scalar loads, which leave the vector
-// memory path to p, buf and img. Word 4 v + j is the lane mask of element j of row v: the decode
-// of an element is one select between scale and -scale. p, buf, img 16-byte aligned; what is
-// left of the range after the whole 1024-element units goes element by element in workgroup 0.
-// What a further source costs follows the number of scalar load requests (three per source and
-// unit here: the scales, two times eight words), not their bytes and not their latency: units of
-// 512 or 256 elements (four and eight requests per 1024 elements) measured 63 and 96 us against
-// 51 us at W = 32, n = 11.2 M, and issuing two or four sources' loads together before the first
-// use changed nothing (profiles/sign1_kernels.txt).
+// Vectorised form (blockwire.hpp block_apply_rows): p, buf, img 16-byte aligned.
 template <bool MOM, bool IMG>
-__global__ __launch_bounds__(256) void sign1_apply_multi_rows_kernel(float* __restrict__ p, S1Srcs srcs, long w_off,
+__global__ __launch_bounds__(256) void sign1_apply_multi_rows_kernel(float* __restrict__ p, BlockSrcs srcs, long w_off,
                                                                      float* __restrict__ buf, long e0, long e1,
                                                                      float lr, float gscale, float momentum, float wd,
                                                                      int first, uint16_t* __restrict__ img) {
-  const long nu = (e1 - e0) >> 10;  // whole 1024-element units
-  const long t0 = e0 + (nu << 10);
-  if (blockIdx.x == 0) {
-    for (long i = t0 + threadIdx.x; i < e1; i += blockDim.x) {
-      const float pv = p[i];
-      const float nv = sgd_tail<MOM>(s1_sum1(srcs, w_off, i), pv, buf + i, lr, gscale, momentum, wd, first);
-      p[i] = nv;
-      if (IMG) img[i] = f2bf(nv);
-    }
-  }
-  const int lane = threadIdx.x & 63;
-  const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
-  for (long u = wave; u < nu; u += nwaves) {
-    // first block of the unit: below 2^23 (n < 2^31), the same in every lane
-    const int b = __builtin_amdgcn_readfirstlane((int)((e0 >> 8) + (u << 2)));
-    const long e = (long)b * kS1Block + lane * 4;  // row v: e + 256 v
-    f32x4 pv[4];
-    float bv[16] = {};
-#pragma unroll
-    for (int v = 0; v < 4; ++v) pv[v] = *reinterpret_cast<const f32x4*>(p + e + 256 * v);
-    if (MOM && !first) {
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(buf + e + 256 * v);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bv[4 * v + j] = t[j];
-      }
-    }
-    float s[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) s[j] = 0.f;
-    for (int k = 0; k < srcs.n; ++k) {
-      const uint8_t* base = srcs.p[k];
-      const s1_cf32 scp = s1_scales(base) + b;
-      const s1_cu64 wp = s1_words(base, w_off) + 4 * (long)b;
-      float sc[4];
-      uint64_t w[16];
-#pragma unroll
-      for (int v = 0; v < 4; ++v) sc[v] = scp[v];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) w[j] = wp[j];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) s[j] = s[j] + s1_deq(s1_lane_bit(w[j]), sc[j >> 2]);
-    }
-#pragma unroll
-    for (int v = 0; v < 4; ++v)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        pv[v][j] = sgd_tail<MOM>(s[4 * v + j], pv[v][j], &bv[4 * v + j], lr, gscale, momentum, wd, first);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) *reinterpret_cast<f32x4*>(p + e + 256 * v) = pv[v];
-    if (MOM) {
-#pragma unroll
-      for (int v = 0; v < 4; ++v)
-        *reinterpret_cast<f32x4*>(buf + e + 256 * v) = (f32x4){bv[4 * v], bv[4 * v + 1], bv[4 * v + 2], bv[4 * v + 3]};
-    }
-    if (IMG) {
-#pragma unroll
-      for (int v = 0; v < 4; ++v)
-        *reinterpret_cast<u32x2*>(img + e + 256 * v) = (u32x2){pack_bf2(pv[v][0], pv[v][1]), pack_bf2(pv[v][2], pv[v][3])};
-    }
-  }
+  block_apply_rows<MOM, IMG, S1Wire>(p, srcs, w_off, buf, e0, e1, lr, gscale, momentum, wd, first, img, blockDim.x);
 }
 
 // dst[i] = [dst[i] +] scale * deq[i] over blocks [blk0, blk1), nothing at or past e1. A wave owns
@@ -266,13 +181,13 @@ __global__ __launch_bounds__(256) void sign1_decode_kernel(const uint8_t* __rest
   const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
   for (long bb = blk0 + wave; bb < blk1; bb += nwaves) {
     const int b = __builtin_amdgcn_readfirstlane((int)bb);
-    const long e = (long)b * kS1Block + lane * 4;
+    const long e = (long)b * kBlock + lane * 4;
     const float sc = s1_scales(payload)[b];
     const s1_cu64 wp = s1_words(payload, w_off) + 4 * (long)b;
     float o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = scale * s1_deq(s1_lane_bit(wp[j]), sc);
-    if (VEC && (long)(b + 1) * kS1Block <= e1) {
+    if (VEC && (long)(b + 1) * kBlock <= e1) {
       f32x4 d = {o[0], o[1], o[2], o[3]};
       if (ADD) {
         const f32x4 t = *reinterpret_cast<const f32x4*>(dst + e);
@@ -292,12 +207,6 @@ __global__ __launch_bounds__(256) void sign1_decode_kernel(const uint8_t* __rest
 
 using namespace psx;
 
-// [off, off + cnt) must start on a block and end on a block or at n
-static bool s1_range_ok(long n, long off, long cnt) {
-  return n > 0 && n <= 0x7fffffffL && off >= 0 && cnt >= 0 && off % kS1Block == 0 && off + cnt <= n &&
-         ((off + cnt) % kS1Block == 0 || off + cnt == n);
-}
-
 extern "C" {
 
 long psx_sign1_payload_bytes(long n) { return s1_layout(n).bytes; }
@@ -307,15 +216,15 @@ long psx_sign1_payload_bytes(long n) { return s1_layout(n).bytes; }
 // fp32 or fp16 (g_fp16). The header is written by the call that covers block 0.
 int psx_sign1_encode(const void* g, int g_fp16, float* resid, long n, void* payload, long off, long cnt,
                      hipStream_t st) {
-  if (!s1_range_ok(n, off, cnt) || (uintptr_t)payload % 16 != 0) return (int)hipErrorInvalidValue;
+  if (!block_range_ok(n, off, cnt) || !al16(payload)) return (int)hipErrorInvalidValue;
   if (cnt == 0) return 0;
-  const S1Layout l = s1_layout(n);
+  const BlockLayout l = s1_layout(n);
   uint8_t* pl = (uint8_t*)payload;
   float* scales = (float*)(pl + l.scales_off);
-  uint64_t* words = (uint64_t*)(pl + l.w_off);
-  const long blk0 = off / kS1Block, blk1 = (off + cnt + kS1Block - 1) / kS1Block;
+  uint64_t* words = (uint64_t*)(pl + l.body_off);
+  const long blk0 = off / kBlock, blk1 = (off + cnt + kBlock - 1) / kBlock;
   int* hdr = off == 0 ? (int*)pl : nullptr;
-  const bool vec = (uintptr_t)resid % 16 == 0 && (uintptr_t)g % (g_fp16 ? 8 : 16) == 0;
+  const bool vec = al16(resid) && (uintptr_t)g % (g_fp16 ? 8 : 16) == 0;
   const dim3 grid(stream_grid((blk1 - blk0) * 64));
   dispatch2(g_fp16 != 0, vec, [&](auto fp16, auto v) {
     hipLaunchKernelGGL((sign1_encode_kernel<wire_t<decltype(fp16)>, decltype(v)::value>), grid, dim3(256), 0, st,
@@ -330,38 +239,27 @@ int psx_sign1_encode(const void* g, int g_fp16, float* resid, long n, void* payl
 // element 0 of the n-element arrays. A payload may share no byte with p, buf or img.
 int psx_sign1_apply_multi(float* p, const void* const* payloads, int nsrc, float* buf, long n, long off, long cnt,
                           float lr, float gscale, float momentum, float wd, int first, void* img, hipStream_t st) {
-  if (nsrc < 1 || nsrc > kMaxSrc || !s1_range_ok(n, off, cnt)) return (int)hipErrorInvalidValue;
-  if (cnt == 0) return 0;
-  const S1Layout l = s1_layout(n);
-  S1Srcs sl{};
-  sl.n = nsrc;
-  const bool aligned = al16(p) && al16(buf) && al16(img);
-  for (int k = 0; k < nsrc; ++k) {
-    const void* s = payloads[k];
-    if (!s || !al16(s)) return (int)hipErrorInvalidValue;
-    if (ranges_overlap(s, (size_t)l.bytes, p, (size_t)n * 4) ||
-        (buf && ranges_overlap(s, (size_t)l.bytes, buf, (size_t)n * 4)) ||
-        (img && ranges_overlap(s, (size_t)l.bytes, img, (size_t)n * 2)))
-      return (int)hipErrorInvalidValue;
-    sl.p[k] = (const uint8_t*)s;
-  }
+  const BlockLayout l = s1_layout(n);
+  BlockSrcs sl{};
+  if (const int e = block_apply_prologue(payloads, nsrc, l.bytes, n, off, cnt, p, buf, img, sl); e != 0 || sl.n == 0)
+    return e;
   const bool mom = buf != nullptr && momentum != 0.f;
   uint16_t* im = (uint16_t*)img;
   const long e0 = off, e1 = off + cnt;
-  if (aligned && cnt >= 1024) {
+  if (al16(p) && al16(buf) && al16(img) && cnt >= 1024) {
     const dim3 grid(stream_grid((cnt >> 10) * 64));
     dispatch2(mom, im != nullptr, [&](auto m, auto i) {
       hipLaunchKernelGGL((sign1_apply_multi_rows_kernel<decltype(m)::value, decltype(i)::value>), grid, dim3(256), 0,
-                         st, p, sl, l.w_off, buf, e0, e1, lr, gscale, momentum, wd, first, im);
+                         st, p, sl, l.body_off, buf, e0, e1, lr, gscale, momentum, wd, first, im);
     });
     return (int)hipGetLastError();
   }
   const dim3 grid(stream_grid(cnt));
   if (mom)
-    hipLaunchKernelGGL(sign1_apply_multi_kernel<true>, grid, dim3(256), 0, st, p, sl, l.w_off, buf, e0, e1, lr,
+    hipLaunchKernelGGL(sign1_apply_multi_kernel<true>, grid, dim3(256), 0, st, p, sl, l.body_off, buf, e0, e1, lr,
                        gscale, momentum, wd, first, im);
   else
-    hipLaunchKernelGGL(sign1_apply_multi_kernel<false>, grid, dim3(256), 0, st, p, sl, l.w_off, buf, e0, e1, lr,
+    hipLaunchKernelGGL(sign1_apply_multi_kernel<false>, grid, dim3(256), 0, st, p, sl, l.body_off, buf, e0, e1, lr,
                        gscale, momentum, wd, first, im);
   return (int)hipGetLastError();
 }
@@ -370,16 +268,16 @@ int psx_sign1_apply_multi(float* p, const void* const* payloads, int nsrc, float
 // byte with the payload).
 int psx_sign1_decode(const void* payload, float* dst, long n, long off, long cnt, float scale, int add,
                      hipStream_t st) {
-  if (!s1_range_ok(n, off, cnt) || (uintptr_t)payload % 16 != 0) return (int)hipErrorInvalidValue;
+  if (!block_range_ok(n, off, cnt) || !al16(payload)) return (int)hipErrorInvalidValue;
   if (cnt == 0) return 0;
-  const S1Layout l = s1_layout(n);
+  const BlockLayout l = s1_layout(n);
   if (ranges_overlap(payload, (size_t)l.bytes, dst, (size_t)n * 4)) return (int)hipErrorInvalidValue;
   const long e1 = off + cnt;
-  const long blk0 = off / kS1Block, blk1 = (e1 + kS1Block - 1) / kS1Block;
+  const long blk0 = off / kBlock, blk1 = (e1 + kBlock - 1) / kBlock;
   const dim3 grid(stream_grid((blk1 - blk0) * 64));
   dispatch2(add != 0, al16(dst), [&](auto a, auto v) {
     hipLaunchKernelGGL((sign1_decode_kernel<decltype(a)::value, decltype(v)::value>), grid, dim3(256), 0, st,
-                       (const uint8_t*)payload, l.w_off, dst, blk0, blk1, e1, scale);
+                       (const uint8_t*)payload, l.body_off, dst, blk0, blk1, e1, scale);
   });
   return (int)hipGetLastError();
 }

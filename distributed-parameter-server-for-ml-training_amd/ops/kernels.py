@@ -645,32 +645,88 @@ def topk_decode_add(payload, dst, scale, kcap):
           "topk_decode_add")
 
 
-def q8_payload_bytes(n: int) -> int:
-    return kernels().psx_q8_payload_bytes(int(n))
+# ---- the block wires (csrc/kernels/blockwire.hpp): q8, sign1 and the q8delta fetch wire. One checked
+# call per operation, given the codec's name and its psx_* entry; the public wrappers bind them.
+
+_GRAD_DTYPES = (torch.float16, torch.float32)
 
 
-def _q8_range(n, off, cnt):
+def _block_payload_bytes(codec: str, n: int) -> int:
+    return getattr(kernels(), f"psx_{codec}_payload_bytes")(int(n))
+
+
+def _block_range(codec, n, off, cnt):
     cnt = n - off if cnt is None else cnt
     assert off % 256 == 0 and 0 <= off and off + cnt <= n and ((off + cnt) % 256 == 0 or off + cnt == n), \
-        "q8 sub-range: 256-aligned start, end on a block or at n"
+        f"{codec} sub-range: 256-aligned start, end on a block or at n"
     return int(off), int(cnt)
 
 
-def _q8_payload_ok(payload, n) -> bool:
-    return payload.dtype == torch.uint8 and payload.is_contiguous() and payload.numel() == q8_payload_bytes(n)
+def _block_payload_ok(codec, payload, n) -> bool:
+    return (payload.dtype == torch.uint8 and payload.is_contiguous()
+            and payload.numel() == _block_payload_bytes(codec, n))
+
+
+def _block_encode(codec, entry, what, src, rw, payload, n, off, cnt, src_dtypes):
+    """The encodes: ``src`` (read: g, fp32 or fp16, or the fp32 arena) and ``rw`` (fp32, read and
+    written back: resid or shadow), >= n elements each, into ``payload``, the whole arena's payload
+    of ``codec``. An entry that takes both gradient dtypes is told which one it got."""
+    n = rw.numel() if n is None else n
+    off, cnt = _block_range(codec, n, off, cnt)
+    assert src.dtype in src_dtypes and src.numel() >= n and src.device == rw.device, f"{entry} {what[0]}"
+    assert rw.dtype == torch.float32 and rw.numel() >= n, f"{entry} {what[1]}"
+    assert _block_payload_ok(codec, payload, n) and payload.device == rw.device, f"{entry} payload"
+    fp16 = (int(src.dtype == torch.float16),) if len(src_dtypes) > 1 else ()
+    check(getattr(kernels(), f"psx_{entry}")(ptr(src), *fp16, ptr(rw), n, ptr(payload), off, cnt, stream_ptr()), entry)
+
+
+def _block_apply_multi(codec, p, payloads, lr, gscale, momentum, wd, buf, first, n, img, off, cnt):
+    entry = f"{codec}_apply_multi"
+    n = p.numel() if n is None else n
+    off, cnt = _block_range(codec, n, off, cnt)
+    assert 1 <= len(payloads) <= 32
+    assert p.dtype == torch.float32 and p.numel() >= n, f"{entry} p"
+    assert all(_block_payload_ok(codec, s, n) and s.device == p.device for s in payloads), entry
+    if buf is not None:
+        assert buf.dtype == torch.float32 and buf.numel() >= n and buf.device == p.device, f"{entry} buf"
+    if img is not None:
+        assert img.dtype == torch.bfloat16 and img.numel() >= n and img.device == p.device, f"{entry} img"
+    arr = (C.c_void_p * len(payloads))(*[s.data_ptr() for s in payloads])
+    check(getattr(kernels(), f"psx_{entry}")(ptr(p), arr, len(payloads), ptr(buf), n, off, cnt, float(lr),
+                                             float(gscale), float(momentum), float(wd), int(first), ptr(img),
+                                             stream_ptr()), entry)
+
+
+def _block_decode(codec, payload, dst, n, scale, add, off, cnt):
+    entry = f"{codec}_decode"
+    n = dst.numel() if n is None else n
+    off, cnt = _block_range(codec, n, off, cnt)
+    assert dst.dtype == torch.float32 and dst.numel() >= n, f"{entry} dst"
+    assert _block_payload_ok(codec, payload, n) and payload.device == dst.device, f"{entry} payload"
+    check(getattr(kernels(), f"psx_{entry}")(ptr(payload), ptr(dst), n, off, cnt, float(scale), int(add),
+                                             stream_ptr()), entry)
+
+
+def q8_payload_bytes(n: int) -> int:
+    return _block_payload_bytes("q8", n)
+
+
+def sign1_payload_bytes(n: int) -> int:
+    return _block_payload_bytes("sign1", n)
 
 
 def q8_encode(g, resid, payload, n=None, off=0, cnt=None):
     """Error-feedback block-scaled int8 encode of (resid + g)[off:off+cnt] into ``payload`` (the
     whole arena's q8 payload, parallel/q8.py); resid keeps acc - deq (csrc/kernels/q8.hip).
     g: fp32 or fp16, >= n elements; resid: fp32, >= n elements."""
-    n = resid.numel() if n is None else n
-    off, cnt = _q8_range(n, off, cnt)
-    assert g.dtype in (torch.float16, torch.float32) and g.numel() >= n and g.device == resid.device, "q8_encode g"
-    assert resid.dtype == torch.float32 and resid.numel() >= n, "q8_encode resid"
-    assert _q8_payload_ok(payload, n) and payload.device == resid.device, "q8_encode payload"
-    check(kernels().psx_q8_encode(ptr(g), int(g.dtype == torch.float16), ptr(resid), n, ptr(payload), off, cnt,
-                                  stream_ptr()), "q8_encode")
+    _block_encode("q8", "q8_encode", "g resid".split(), g, resid, payload, n, off, cnt, _GRAD_DTYPES)
+
+
+def sign1_encode(g, resid, payload, n=None, off=0, cnt=None):
+    """Error-feedback 1-bit sign encode of (resid + g)[off:off+cnt] into ``payload`` (the whole
+    arena's sign1 payload, parallel/sign1.py); resid keeps acc - deq (csrc/kernels/sign1.hip).
+    g: fp32 or fp16, >= n elements; resid: fp32, >= n elements."""
+    _block_encode("sign1", "sign1_encode", "g resid".split(), g, resid, payload, n, off, cnt, _GRAD_DTYPES)
 
 
 def fetchq8_encode(arena, shadow, payload, n=None, off=0, cnt=None):
@@ -678,102 +734,34 @@ def fetchq8_encode(arena, shadow, payload, n=None, off=0, cnt=None):
     int8 of (arena - shadow)[off:off+cnt] into ``payload`` (the whole arena's q8 payload); shadow
     becomes shadow + deq, what q8_decode(add=True) leaves on a worker (csrc/kernels/q8.hip).
     arena, shadow: fp32, >= n elements."""
-    n = shadow.numel() if n is None else n
-    off, cnt = _q8_range(n, off, cnt)
-    assert arena.dtype == torch.float32 and arena.numel() >= n and arena.device == shadow.device, \
-        "fetchq8_encode arena"
-    assert shadow.dtype == torch.float32 and shadow.numel() >= n, "fetchq8_encode shadow"
-    assert _q8_payload_ok(payload, n) and payload.device == shadow.device, "fetchq8_encode payload"
-    check(kernels().psx_fetchq8_encode(ptr(arena), ptr(shadow), n, ptr(payload), off, cnt, stream_ptr()),
-          "fetchq8_encode")
+    _block_encode("q8", "fetchq8_encode", "arena shadow".split(), arena, shadow, payload, n, off, cnt,
+                  (torch.float32,))
 
 
 def q8_apply_multi(p, payloads, lr, gscale=1.0, momentum=0.0, wd=0.0, buf=None, first=False, n=None, img=None, off=0,
                    cnt=None):
     """p[off:off+cnt] -= lr*(gscale * sum_k deq(payloads[k]) + wd*p) [momentum]: the server update
     straight from the gathered q8 payloads, decoded and summed in fp32 in list order (same update
-    tail as sgd_apply_multi). At most 32 payloads; one payload is the async / W = 1 apply."""
-    n = p.numel() if n is None else n
-    off, cnt = _q8_range(n, off, cnt)
-    assert 1 <= len(payloads) <= 32
-    assert p.dtype == torch.float32 and p.numel() >= n, "q8_apply_multi p"
-    assert all(_q8_payload_ok(s, n) and s.device == p.device for s in payloads), "q8_apply_multi"
-    if buf is not None:
-        assert buf.dtype == torch.float32 and buf.numel() >= n and buf.device == p.device, "q8_apply_multi buf"
-    if img is not None:
-        assert img.dtype == torch.bfloat16 and img.numel() >= n and img.device == p.device, "q8_apply_multi img"
-    arr = (C.c_void_p * len(payloads))(*[s.data_ptr() for s in payloads])
-    check(kernels().psx_q8_apply_multi(ptr(p), arr, len(payloads), ptr(buf), n, off, cnt, float(lr), float(gscale),
-                                       float(momentum), float(wd), int(first), ptr(img), stream_ptr()),
-          "q8_apply_multi")
-
-
-def q8_decode(payload, dst, n=None, scale=1.0, add=False, off=0, cnt=None):
-    """dst[off:off+cnt] = [dst +] scale * deq(payload) (fp32 dst of >= n elements)."""
-    n = dst.numel() if n is None else n
-    off, cnt = _q8_range(n, off, cnt)
-    assert dst.dtype == torch.float32 and dst.numel() >= n, "q8_decode dst"
-    assert _q8_payload_ok(payload, n) and payload.device == dst.device, "q8_decode payload"
-    check(kernels().psx_q8_decode(ptr(payload), ptr(dst), n, off, cnt, float(scale), int(add), stream_ptr()),
-          "q8_decode")
-
-
-def sign1_payload_bytes(n: int) -> int:
-    return kernels().psx_sign1_payload_bytes(int(n))
-
-
-def _sign1_range(n, off, cnt):
-    cnt = n - off if cnt is None else cnt
-    assert off % 256 == 0 and 0 <= off and off + cnt <= n and ((off + cnt) % 256 == 0 or off + cnt == n), \
-        "sign1 sub-range: 256-aligned start, end on a block or at n"
-    return int(off), int(cnt)
-
-
-def _sign1_payload_ok(payload, n) -> bool:
-    return payload.dtype == torch.uint8 and payload.is_contiguous() and payload.numel() == sign1_payload_bytes(n)
-
-
-def sign1_encode(g, resid, payload, n=None, off=0, cnt=None):
-    """Error-feedback 1-bit sign encode of (resid + g)[off:off+cnt] into ``payload`` (the whole
-    arena's sign1 payload, parallel/sign1.py); resid keeps acc - deq (csrc/kernels/sign1.hip).
-    g: fp32 or fp16, >= n elements; resid: fp32, >= n elements."""
-    n = resid.numel() if n is None else n
-    off, cnt = _sign1_range(n, off, cnt)
-    assert g.dtype in (torch.float16, torch.float32) and g.numel() >= n and g.device == resid.device, "sign1_encode g"
-    assert resid.dtype == torch.float32 and resid.numel() >= n, "sign1_encode resid"
-    assert _sign1_payload_ok(payload, n) and payload.device == resid.device, "sign1_encode payload"
-    check(kernels().psx_sign1_encode(ptr(g), int(g.dtype == torch.float16), ptr(resid), n, ptr(payload), off, cnt,
-                                     stream_ptr()), "sign1_encode")
+    tail as sgd_apply_multi). At most 32 payloads; one payload is the async / W = 1 apply. A
+    payload may share no byte with p, buf or img."""
+    _block_apply_multi("q8", p, payloads, lr, gscale, momentum, wd, buf, first, n, img, off, cnt)
 
 
 def sign1_apply_multi(p, payloads, lr, gscale=1.0, momentum=0.0, wd=0.0, buf=None, first=False, n=None, img=None,
                       off=0, cnt=None):
-    """p[off:off+cnt] -= lr*(gscale * sum_k deq(payloads[k]) + wd*p) [momentum]: the server update
-    straight from the gathered sign1 payloads, decoded and summed in fp32 in list order (same
-    update tail as sgd_apply_multi). At most 32 payloads; one payload is the async / W = 1 apply."""
-    n = p.numel() if n is None else n
-    off, cnt = _sign1_range(n, off, cnt)
-    assert 1 <= len(payloads) <= 32
-    assert p.dtype == torch.float32 and p.numel() >= n, "sign1_apply_multi p"
-    assert all(_sign1_payload_ok(s, n) and s.device == p.device for s in payloads), "sign1_apply_multi"
-    if buf is not None:
-        assert buf.dtype == torch.float32 and buf.numel() >= n and buf.device == p.device, "sign1_apply_multi buf"
-    if img is not None:
-        assert img.dtype == torch.bfloat16 and img.numel() >= n and img.device == p.device, "sign1_apply_multi img"
-    arr = (C.c_void_p * len(payloads))(*[s.data_ptr() for s in payloads])
-    check(kernels().psx_sign1_apply_multi(ptr(p), arr, len(payloads), ptr(buf), n, off, cnt, float(lr),
-                                          float(gscale), float(momentum), float(wd), int(first), ptr(img),
-                                          stream_ptr()), "sign1_apply_multi")
+    """q8_apply_multi for sign1 payloads."""
+    _block_apply_multi("sign1", p, payloads, lr, gscale, momentum, wd, buf, first, n, img, off, cnt)
+
+
+def q8_decode(payload, dst, n=None, scale=1.0, add=False, off=0, cnt=None):
+    """dst[off:off+cnt] = [dst +] scale * deq(payload) (fp32 dst of >= n elements, sharing no byte
+    with the payload)."""
+    _block_decode("q8", payload, dst, n, scale, add, off, cnt)
 
 
 def sign1_decode(payload, dst, n=None, scale=1.0, add=False, off=0, cnt=None):
-    """dst[off:off+cnt] = [dst +] scale * deq(payload) (fp32 dst of >= n elements)."""
-    n = dst.numel() if n is None else n
-    off, cnt = _sign1_range(n, off, cnt)
-    assert dst.dtype == torch.float32 and dst.numel() >= n, "sign1_decode dst"
-    assert _sign1_payload_ok(payload, n) and payload.device == dst.device, "sign1_decode payload"
-    check(kernels().psx_sign1_decode(ptr(payload), ptr(dst), n, off, cnt, float(scale), int(add), stream_ptr()),
-          "sign1_decode")
+    """q8_decode for a sign1 payload."""
+    _block_decode("sign1", payload, dst, n, scale, add, off, cnt)
 
 
 def _wire_srcs(srcs, n, dev, state, what):

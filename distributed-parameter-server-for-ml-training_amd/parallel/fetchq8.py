@@ -11,7 +11,8 @@ element: two-way compression with error feedback, as in DoubleSqueeze (Tang et a
   later fetch encodes ``arena - shadow`` per block of 256 consecutive arena elements and advances
   ``shadow`` by what the payload decodes to — one streaming pass, csrc/kernels/q8.hip
   fetchq8_encode;
-* wire: the payload of parallel/q8.py (``Q8B1``), unchanged;
+* wire: the payload of parallel/q8.py (``Q8B1``), unchanged, from the same quantiser
+  (``q8.quantise``) in parallel/blockwire.py's frame;
 * worker: ``local_arena = local_arena + deq``, which is ``q8.decode(add=True, scale=1.0)``.
 
 The arithmetic is fixed so that the torch CPU path here and the HIP kernels agree bit for bit::
@@ -45,6 +46,7 @@ from __future__ import annotations
 
 import torch
 
+from . import blockwire as BW
 from . import q8
 
 payload_bytes = q8.payload_bytes
@@ -53,33 +55,21 @@ empty_payload = q8.empty_payload
 
 def encode_into(arena: torch.Tensor, shadow: torch.Tensor, payload: torch.Tensor, n: int, off: int = 0, cnt=None):
     """Encode (arena - shadow)[off:off+cnt] into ``payload`` and leave shadow = shadow + deq there."""
-    off, cnt = q8._range(n, off, cnt)
+    off, cnt = BW.check_range("q8", n, off, cnt)
     if shadow.device.type == "cuda":
         from ..ops import kernels as K
 
         K.fetchq8_encode(arena, shadow, payload, n, off, cnt)
         return payload
-    hdr, scales, q = q8.views(payload, n)
+    q8.views(payload, n)
     if off == 0:
-        hdr.copy_(torch.tensor([q8.MAGIC, n, q8.BLOCK, q8.num_blocks(n)], dtype=torch.int32))
+        BW.write_header(payload, q8.MAGIC, n)
     if cnt == 0:
         return payload
     sh = q8._blocks(shadow[off:off + cnt])
-    d = q8._blocks(arena[off:off + cnt] - shadow[off:off + cnt])
-    a = d.abs()
-    nonfinite = ~(a <= q8._FMAX)  # NaN or Inf
-    bad = nonfinite.any(dim=1)
-    amax = torch.where(nonfinite, torch.zeros_like(a), a).amax(dim=1)
-    c127 = torch.full_like(amax, 127.0)
-    scale = torch.where(bad, torch.full_like(amax, float("nan")), amax / c127)
-    inv = torch.where(~bad & (amax > 0), c127 / amax, torch.zeros_like(amax))
-    r = torch.round(d * inv[:, None])
-    r = torch.where(r.isnan(), torch.zeros_like(r), r).clamp_(-127.0, 127.0)
-    deq = r * scale[:, None]
+    scale, r, deq = q8.quantise(q8._blocks(arena[off:off + cnt] - shadow[off:off + cnt]))
     shadow[off:off + cnt] = (sh + deq).view(-1)[:cnt]
-    q[off:off + cnt] = r.view(-1)[:cnt].to(torch.int8)
-    b0 = off // q8.BLOCK
-    scales[b0:b0 + scale.numel()] = scale
+    q8.put(payload, n, off, cnt, scale, r)
     return payload
 
 

@@ -10,6 +10,8 @@ adam_v / adam_t, agg, _lars_tab, _guard_state, ...). Its parts:
 * ``adam``: the rule counts its updates in adam_t and keeps both moments (checkpoint / resume);
 * ``table``: the rule keeps per-tensor ratios (the device segment table, ops/kernels.py LarsTable);
 * ``scatters(cfg)``: a top-k payload may be scattered straight into the parameters;
+* ``device_payload(s, codec, payloads, weight, img)``: the device form that decodes q8 / sign1
+  payloads inside the update (the wrapper parallel/pushcodec.py names); None unless defined;
 * ``device(s, srcs, weight, lo, hi, img, summed)``: the launches, through the wrappers of
   ops/kernels.py, always called as attributes of that module;
 * ``host(s, srcs, weight, lo, hi, summed)``: the same formula in torch on a CPU arena; False when
@@ -101,8 +103,7 @@ def _scalars(fn: str, *a, **hp):
 class Rule:
     """The parts of a rule that have a default (the module docstring lists them all)."""
     whole, adam, table, refusal = False, False, False, ""
-    device_q8 = None  # the device form that decodes q8 payloads inside the update, where there is one
-    device_sign1 = None  # the same for sign1 payloads
+    device_payload = None  # the in-kernel decode of q8 / sign1 payloads, where the rule has one
 
     def scatters(self, cfg) -> bool:
         return False
@@ -111,30 +112,13 @@ class Rule:
         return {}
 
 
-class SGD(Rule):
-    """p <- p - lr * (weight * g [+ wd p]) [momentum]: csrc/kernels/optim.hip (q8 / sign1
-    payloads: csrc/kernels/q8.hip / sign1.hip, decoded inside the update). Element-wise: any range
-    is legal, and the ranges of one round share the momentum 'first step' flag."""
-
-    def scatters(self, cfg) -> bool:
-        return not cfg.momentum and not cfg.weight_decay  # no optimizer state to keep in step
+class _SGDTail(Rule):
+    """What the rules that end in the SGD tail share: its arguments, and its host form."""
 
     def _kw(self, s, weight, lo, hi, img) -> dict:
         return dict(gscale=weight, momentum=s.cfg.momentum, wd=s.cfg.weight_decay,
                     buf=s.momentum_buf[lo:hi] if s.momentum_buf is not None else None, first=s._mom_first,
                     n=hi - lo, img=img)
-
-    def device(self, s, srcs, weight, lo, hi, img, summed):
-        if summed:
-            K.sgd_apply(s.params[lo:hi], srcs[0], s.lr, **self._kw(s, weight, lo, hi, img))
-        else:
-            K.sgd_apply_multi(s.params[lo:hi], first_n(srcs, hi - lo), s.lr, **self._kw(s, weight, lo, hi, img))
-
-    def device_q8(self, s, payloads, weight, img):
-        K.q8_apply_multi(s.params, payloads, s.lr, **self._kw(s, weight, 0, s.n, img))
-
-    def device_sign1(self, s, payloads, weight, img):
-        K.sign1_apply_multi(s.params, payloads, s.lr, **self._kw(s, weight, 0, s.n, img))
 
     def host(self, s, srcs, weight, lo, hi, summed):
         p = s.params[lo:hi]
@@ -151,7 +135,25 @@ class SGD(Rule):
         p.sub_(s.lr * d)
 
 
-class Guard(SGD):
+class SGD(_SGDTail):
+    """p <- p - lr * (weight * g [+ wd p]) [momentum]: csrc/kernels/optim.hip (q8 / sign1
+    payloads: csrc/kernels/q8.hip / sign1.hip, decoded inside the update). Element-wise: any range
+    is legal, and the ranges of one round share the momentum 'first step' flag."""
+
+    def scatters(self, cfg) -> bool:
+        return not cfg.momentum and not cfg.weight_decay  # no optimizer state to keep in step
+
+    def device(self, s, srcs, weight, lo, hi, img, summed):
+        if summed:
+            K.sgd_apply(s.params[lo:hi], srcs[0], s.lr, **self._kw(s, weight, lo, hi, img))
+        else:
+            K.sgd_apply_multi(s.params[lo:hi], first_n(srcs, hi - lo), s.lr, **self._kw(s, weight, lo, hi, img))
+
+    def device_payload(self, s, codec, payloads, weight, img):
+        getattr(K, codec.in_kernel)(s.params, payloads, s.lr, **self._kw(s, weight, 0, s.n, img))
+
+
+class Guard(_SGDTail):
     """--clip-norm / --skip-nonfinite around the SGD rule: S = sum s^2 of the round's fp32 sum,
     norm = weight * sqrt(S); S not finite: the round is skipped (parameters, momentum buffer and
     fetch image untouched; it still counts as a round, and consumes the momentum 'first step' flag:
@@ -164,7 +166,6 @@ class Guard(SGD):
     whole = True
     refusal = ("--clip-norm / --skip-nonfinite need the whole gradient's norm before the first parameter moves: a "
                "partial range [{lo}, {hi}) of {n} cannot be applied (no bucketed or sharded updates)")
-    device_q8, device_sign1, scatters = None, None, Rule.scatters
 
     def device(self, s, srcs, weight, lo, hi, img, summed):
         stage(s, srcs, "guard", s._guard_state, lr=s.lr, clip_norm=s.cfg.clip_norm, **self._kw(s, weight, lo, hi, img))
@@ -185,13 +186,13 @@ class Guard(SGD):
         h["norm_last"] = norm
         h["norm_max"] = max(h["norm_max"], norm)
         h["norm_sum"] += norm
-        SGD.host(self, s, [s.agg], float(np.float32(weight) * coef), lo, hi, True)
+        _SGDTail.host(self, s, [s.agg], float(np.float32(weight) * coef), lo, hi, True)
 
     def metrics(self, s) -> dict:
         return {"gradient_guard": s.guard_counters()}
 
 
-class LARS(SGD):
+class LARS(_SGDTail):
     """--optimizer lars: d = lambda_t * (weight * s + wd * w) for tensors with ndim > 1, lambda_t =
     trust * |w| / (weight * |s| + wd * |w| + eps) (1 when a norm is 0); d = weight * s for 1-D
     tensors; then the momentum form of SGD. Device: the two launches of csrc/kernels/lars.hip; CPU
@@ -200,7 +201,6 @@ class LARS(SGD):
     whole = table = True
     refusal = ("--optimizer lars needs every tensor's norm before its first element moves: a partial range "
                "[{lo}, {hi}) of {n} cannot be applied (no bucketed or sharded updates)")
-    device_q8, device_sign1, scatters = None, None, Rule.scatters
 
     def device(self, s, srcs, weight, lo, hi, img, summed):
         s._ratios_applied = True

@@ -31,7 +31,7 @@ from ..models.resnet import MODEL_INPUT, build_model
 from ..utils import metrics as M
 from ..utils.data import DeviceDataset, shard_range, steps_per_epoch
 from . import control as CP
-from . import elastic
+from . import elastic, pushcodec
 from .codec import FetchCodec, WeightWire, weight_image_enabled
 from .compute import make_compute
 from .graph_round import GraphRoundChannel, graph_round_enabled
@@ -678,17 +678,8 @@ def _server_rounds(cfg, server, chan, steps, device, skip, t, ctx):
         if hasattr(chan, "drain"):
             chan.drain()
         return
-    if cfg.codec == "topk":
-        from .topk import empty_payload
-
-        zeros = empty_payload(server.n, cfg.topk_ratio, device)  # contributes no entries to the gather
-    elif cfg.codec in ("q8", "sign1"):
-        from . import q8, sign1
-
-        # rank 0's slot in the gather; the channel drops it
-        zeros = (q8 if cfg.codec == "q8" else sign1).empty_payload(server.n, device)
-    else:
-        zeros = torch.zeros(server.n, dtype=_wire_dtype(cfg), device=device)
+    # rank 0's contribution: zeros to a reduce, an empty payload to a gather
+    zeros = pushcodec.CODECS[cfg.codec].empty(server.n, device, cfg.topk_ratio)
     zbuf = torch.zeros(server.layout.buffer_numel, dtype=torch.float32, device=device) if cfg.bn_sync else None
     skip_b = rounds_to_batches(skip, steps, K)  # checkpointed rounds -> batches (window aligned)
     done = skip_b

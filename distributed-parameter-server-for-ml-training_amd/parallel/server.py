@@ -29,7 +29,8 @@ from ..utils import metrics as M
 from ..ops import kernels as K
 from ..utils import trace
 from . import control as CP
-from . import fetchq8, q8, sign1, topk
+from . import fetchq8, topk
+from . import pushcodec as PC
 from . import rules as R
 from .core import APPLY, WAIT, ServerCore
 
@@ -41,13 +42,6 @@ def arena_sha256(arena: torch.Tensor) -> str:
     import hashlib
 
     return hashlib.sha256(arena.detach().to("cpu", torch.float32).contiguous().numpy().tobytes()).hexdigest()[:32]
-
-
-def _wire_bytes(grads: torch.Tensor, n: int) -> int:
-    """Bytes one push moves: a q8 / sign1 payload whole, otherwise the first n elements of the buffer."""
-    if grads.dtype == torch.uint8:
-        return grads.numel()
-    return min(n, grads.numel()) * grads.element_size()
 
 
 class ParameterServer:
@@ -147,36 +141,30 @@ class ParameterServer:
         if self._dc:
             self._apply_dc(grads, weight, worker_id)
             return self.finish_round_apply(self._time_end(t0))
-        if grads.dtype == torch.int32:  # top-k payload (parallel/topk.py)
-            if self.rule.scatters(self.cfg):
-                # no optimizer state: scatter straight into the fp32 master parameters
-                topk.decode_add(grads, self.params, -self.lr * weight, self._kcap)
-                self._wire_stale = True  # the bf16 image was not written by this update
-                return self.finish_round_apply(self._time_end(t0))
-            grads = self._dense_of(grads)
-        if grads.dtype == torch.uint8:  # q8 / sign1 payload: decoded inside the update
-            self._apply_payloads([grads], weight)
-        else:
+        codec = self.codec_of(grads)
+        if codec is PC.CODECS["topk"] and self.rule.scatters(self.cfg):
+            # no optimizer state: scatter straight into the fp32 master parameters
+            topk.decode_add(grads, self.params, -self.lr * weight, topk.topk_k(self.n, self.cfg.topk_ratio))
+            self._wire_stale = True  # the bf16 image was not written by this update
+            return self.finish_round_apply(self._time_end(t0))
+        if codec.reducible:
             self.apply_range(grads[: self.n], weight, 0, self.n)
+        else:  # a payload: decoded by the update entry
+            self._apply_payloads([grads], weight)
         return self.finish_round_apply(self._time_end(t0))
 
     def _apply_payloads(self, payloads: list, weight: float):
-        """The update from q8 or sign1 payloads (one codec per list), decoded and summed in fp32 in
-        list order (update_range)."""
+        """The update from top-k, q8 or sign1 payloads (one codec per list), decoded and summed in
+        fp32 in list order (update_range)."""
         self.update_range(payloads, weight, 0, self.n)
 
-    _apply_q8 = _apply_payloads  # the name from before sign1 shared the route
+    def codec_of(self, t: torch.Tensor):
+        """The push codec (parallel/pushcodec.py) of a pushed tensor, the configured one preferred."""
+        return PC.of_payload(t, self.n, self.cfg.codec)
 
-    def _payload_codec(self, payload: torch.Tensor):
-        """The codec module (q8 or sign1) of a uint8 payload, told on the host by its byte length
-        — the configured codec's first, where an arena of a few elements gives both the same —
-        never by reading the device header back."""
-        own = {"q8": q8, "sign1": sign1}.get(self.cfg.codec)
-        for m in ((own,) if own is not None else ()) + (q8, sign1):
-            if payload.numel() == m.payload_bytes(self.n):
-                return m
-        raise ValueError(f"a uint8 push of {payload.numel()} bytes is neither a q8 nor a sign1 payload of "
-                         f"{self.n} parameters")
+    def _dense_of(self, t: torch.Tensor, out: torch.Tensor | None = None, add: bool = False):
+        """out = [out +] the dense fp32 gradient of a push of any codec (default: the aggregation buffer)."""
+        return self.codec_of(t).decode(t, self.n, self._agg() if out is None else out, add, self.cfg.topk_ratio)
 
     # ------------------------------------------------------------------ the one update entry
     _IMG_OF_WIRE = object()
@@ -186,8 +174,9 @@ class ParameterServer:
         here. ``srcs``: fp16 / fp32 wires that each hold the gradient of exactly that range in their
         first hi - lo elements, summed in fp32 in list order, or the aggregation buffer itself (a
         decoded or accumulated sum); ``summed``: the one source already is the round's sum, taken
-        as is. q8 / sign1 payloads (whole range): decoded inside the kernel by a rule that has such a
-        device form, otherwise into the aggregation buffer first. A rule that needs the whole arena
+        as is. Payloads (whole range; their codec is told by parallel/pushcodec.py): q8 / sign1 are
+        decoded inside the kernel by a rule that has such a device form (``device_payload``), every
+        other case one after another into the aggregation buffer first. A rule that needs the whole arena
         refuses a partial range. ``img``: the bf16 image slice that receives the updated range, on
         the device in the same pass (default: the weight wire's, which an ``img`` of the caller's,
         and every host form, leaves stale). Several ranges of one round share the momentum 'first
@@ -200,10 +189,10 @@ class ParameterServer:
         on_device, own_img = self.device.type == "cuda", img is not self._IMG_OF_WIRE
         if on_device and not own_img:
             img = self.wire.img[lo:hi] if self.wire is not None else None
-        if srcs[0].dtype == torch.uint8:
-            in_kernel = rule.device_sign1 if self._payload_codec(srcs[0]) is sign1 else rule.device_q8
-            if on_device and in_kernel is not None:
-                return in_kernel(self, srcs, weight, img)
+        codec = self.codec_of(srcs[0])
+        if not codec.reducible:
+            if on_device and codec.in_kernel is not None and rule.device_payload is not None:
+                return rule.device_payload(self, codec, srcs, weight, img)
             for i, p in enumerate(srcs):
                 self._dense_of(p, add=i > 0)
             srcs, summed = [self.agg], True
@@ -255,7 +244,7 @@ class ParameterServer:
             self.dc_uncompensated += 1
         else:
             self.dc_compensated += 1
-        if grads.dtype in (torch.int32, torch.uint8):
+        if not self.codec_of(grads).reducible:
             grads = self._dense_of(grads)
         g = grads[: self.n]
         if bak is None and self._dc_ms is None:  # nothing of the DC form is left: the plain update
@@ -318,20 +307,6 @@ class ParameterServer:
                 keep.append(pairs)
         self._ev_pending = keep
 
-    @property
-    def _kcap(self) -> int:
-        return topk.topk_k(self.n, self.cfg.topk_ratio)
-
-    def _dense_of(self, payload: torch.Tensor, out: torch.Tensor | None = None, add: bool = False):
-        """Top-k / q8 / sign1 payload -> dense fp32 gradient (into the aggregation buffer by default)."""
-        if out is None:
-            out = self._agg()
-        if payload.dtype == torch.uint8:
-            return self._payload_codec(payload).decode(payload, self.n, out=out, add=add)
-        if not add:
-            out.zero_()
-        return topk.decode_add(payload, out, 1.0, self._kcap)
-
     def apply_range(self, g: torch.Tensor, weight: float, lo: int, hi: int):
         """The update restricted to params[lo:hi] (g holds exactly that slice): one bucket of a
         backward-overlapped sync round (parallel/overlap.py). Several ranges of one round share
@@ -387,14 +362,6 @@ class ParameterServer:
         if self.agg is None:
             self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device)
         return self.agg
-
-    def _accumulate(self, grads: torch.Tensor, first: bool):
-        if grads.dtype in (torch.int32, torch.uint8):
-            self._dense_of(grads, add=not first)
-        elif first:
-            self._agg().copy_(grads[: self.n])
-        else:
-            self._agg().add_(grads[: self.n].to(torch.float32))
 
     # ------------------------------------------------------------------ RPC surface
     def register_worker(self, worker_name: str = "worker-node", requested_id: int = -1):
@@ -470,7 +437,7 @@ class ParameterServer:
         completes, then apply the average. Async: staleness check + weighted apply.
         ``buffers`` (--bn-sync): the worker's BN running statistics, counted only when the core
         takes the push into the round (a duplicate / unknown / rejected push contributes nothing)."""
-        self.bytes_pushed += _wire_bytes(grads, self.n)
+        self.bytes_pushed += self.codec_of(grads).wire_bytes(grads, self.n)
         res = self.core.on_push(worker_id, local_step)
         self.last_push = res
         if buffers is not None and (res.decision in (WAIT, APPLY) if self.cfg.mode == "sync" else res.accepted):
@@ -480,11 +447,9 @@ class ParameterServer:
                 # reference: pending[worker_id] = grads (overwrites), average over the dict
                 # entries when the push counter reaches total_workers (server.py:264-288)
                 if res.decision in (WAIT, APPLY):
-                    self._pending[worker_id] = (self._dense_of(grads, torch.zeros(self.n, device=self.device))
-                                                if grads.dtype in (torch.int32, torch.uint8)
-                                                else grads[: self.n].to(torch.float32).clone())
+                    self._pending[worker_id] = self._dense_of(grads, torch.zeros(self.n, device=self.device))
                 if res.apply:
-                    self._accumulate(sum(self._pending.values()), True)
+                    self._dense_of(sum(self._pending.values()))
                     self._pending.clear()
                     self.apply(self.agg, res.weight)
                     self._commit_buffers()
@@ -493,20 +458,11 @@ class ParameterServer:
                 # single-contribution round (W == 1): apply straight from the wire buffer — a dense
                 # wire through the collective rounds' kernel (apply_sources with one source), so a
                 # loopback round and a one-worker RCCL round (a shrunk sync job) give the same bits
-                if grads.dtype == torch.int32:  # decoded into the dense buffer first, as apply_gathered
-                    self._dense_of(grads)
-                    self.apply(self.agg, res.weight)
-                elif grads.dtype == torch.uint8:  # one-source payload apply, as apply_payload_sources
-                    self.apply(grads, res.weight)
-                else:
-                    trace.mark("psx.apply")
-                    t0 = self._time_begin()
-                    self.apply_range_sources([grads], res.weight, 0, self.n)
-                    self.finish_round_apply(self._time_end(t0))
+                self._update_round([grads], res.weight)
                 self._commit_buffers()
                 return True
             if res.decision in (WAIT, APPLY):
-                self._accumulate(grads, self._round_count == 0)
+                self._dense_of(grads, add=self._round_count != 0)
                 self._round_count += 1
             if res.apply:
                 self.apply(self.agg, res.weight)
@@ -564,78 +520,46 @@ class ParameterServer:
     JobFinished = job_finished
 
     # ------------------------------------------------------------------ sync (collective) path
-    def apply_reduced(self, summed: torch.Tensor, members: list[int], local_steps: list[int],
-                      buffers_sum: torch.Tensor | None = None) -> bool:
-        """Bookkeeping + update for one sync round whose gradient sum arrived by RCCL reduce."""
+    def apply_round(self, srcs: list, members: list[int], local_steps: list[int],
+                    buffers_sum: torch.Tensor | None = None, summed: bool = False) -> bool:
+        """Bookkeeping + update for one sync round whose contributions reached rank 0 by a
+        collective: ``srcs`` is the reduced sum (``summed``) or one gathered wire or payload per
+        source (_update_round). True when the round's barrier completed and the update ran."""
         res = None
         for wid, ls in zip(members, local_steps):
             res = self.core.on_push(wid, ls)
-        self.bytes_pushed += len(members) * self.n * summed.element_size()
-        if res is not None and res.apply:
-            self.apply(summed, res.weight)
-            if buffers_sum is not None:
-                self.set_buffers_from_sum(buffers_sum, len(members))
-            return True
-        return False
-
-    def apply_sources(self, srcs: list, members: list[int], local_steps: list[int],
-                      buffers_sum: torch.Tensor | None = None) -> bool:
-        """Sync round whose W dense wires were gathered to rank 0 (one per contributing worker):
-        decoded and summed in fp32 in list order inside the update (kernels.sgd_apply_multi),
-        then p -= lr * sum / W — the reference's decompress + aggregate + apply
-        (server.py:126-169, 232-237) without an fp16 running sum."""
-        res = None
-        for wid, ls in zip(members, local_steps):
-            res = self.core.on_push(wid, ls)
-        self.bytes_pushed += sum(s[: self.n].numel() * s.element_size() for s in srcs)
+        if summed:  # the reduce moved every member's wire
+            self.bytes_pushed += len(members) * self.n * srcs[0].element_size()
+        elif srcs:
+            codec = self.codec_of(srcs[0])
+            # a top-k gather holds a slot per rank, a dedicated server's empty one too: the members' count
+            counted = srcs[: max(1, len(members))] if codec is PC.CODECS["topk"] else srcs
+            self.bytes_pushed += sum(codec.wire_bytes(s, self.n) for s in counted)
         if res is None or not res.apply:
             return False
-        trace.mark("psx.apply")
-        t0 = self._time_begin()
-        self.update_range(srcs, res.weight, 0, self.n)
-        self.finish_round_apply(self._time_end(t0))
+        self._update_round(list(srcs), res.weight, summed)
         if buffers_sum is not None:
             self.set_buffers_from_sum(buffers_sum, len(members))
         return True
 
-    def apply_gathered(self, payloads: list, members: list[int], local_steps: list[int],
-                       buffers_sum: torch.Tensor | None = None) -> bool:
-        """Sync round with top-k payloads gathered to rank 0: decode all into one dense fp32
-        sum, then the usual averaged apply."""
-        res = None
-        for wid, ls in zip(members, local_steps):
-            res = self.core.on_push(wid, ls)
-        self.bytes_pushed += sum(p.numel() * 4 for p in payloads[: max(1, len(members))])
-        if res is not None and res.apply:
-            for i, p in enumerate(payloads):
-                self._dense_of(p, add=i > 0)
-            self.apply(self.agg, res.weight)
-            if buffers_sum is not None:
-                self.set_buffers_from_sum(buffers_sum, len(members))
-            return True
-        return False
-
-    def apply_payload_sources(self, payloads: list, members: list[int], local_steps: list[int],
-                              buffers_sum: torch.Tensor | None = None) -> bool:
-        """Sync round whose W q8 or sign1 payloads were gathered to rank 0 (one per contributing
-        worker): the bookkeeping of apply_sources, then one launch that decodes and sums them in
-        fp32 in list order inside the update (kernels.q8_apply_multi / sign1_apply_multi) — no dense
-        staging buffer."""
-        res = None
-        for wid, ls in zip(members, local_steps):
-            res = self.core.on_push(wid, ls)
-        self.bytes_pushed += sum(p.numel() for p in payloads)
-        if res is None or not res.apply:
-            return False
+    def _update_round(self, srcs: list, weight: float, summed: bool = False):
+        """One timed update from a round's sources, closed by finish_round_apply. A reduced sum
+        (``summed``) is taken as is; dense wires are summed in fp32 in list order inside the kernel
+        (the reference's decompress + aggregate + apply, server.py:126-169, 232-237, without an
+        fp16 running sum); payloads are decoded by the update entry (update_range)."""
         trace.mark("psx.apply")
         t0 = self._time_begin()
-        self._apply_payloads(list(payloads), res.weight)
+        self.update_range([srcs[0][: self.n]] if summed else srcs, weight, 0, self.n, summed=summed)
         self.finish_round_apply(self._time_end(t0))
-        if buffers_sum is not None:
-            self.set_buffers_from_sum(buffers_sum, len(members))
-        return True
 
-    apply_q8_sources = apply_payload_sources  # the name from before sign1 shared the route
+    # the rounds by the name of how their sources arrived (channels, tests)
+    def apply_reduced(self, summed, members, local_steps, buffers_sum=None) -> bool:
+        return self.apply_round([summed], members, local_steps, buffers_sum, summed=True)
+
+    def apply_sources(self, srcs, members, local_steps, buffers_sum=None) -> bool:
+        return self.apply_round(srcs, members, local_steps, buffers_sum)
+
+    apply_gathered = apply_payload_sources = apply_sources
 
     # ------------------------------------------------------------------ checkpoint
     def checkpoint(self, path: str | None = None) -> str:
@@ -732,15 +656,8 @@ class ParameterServer:
         expected = expected if expected is not None else len(rank_of) + (1 if local_queue is not None else 0)
         finished = set()
         n = self.n
-        if self.cfg.codec == "topk":
-            words = topk.payload_words(self._kcap)
-            slots = {w: torch.empty(words, dtype=torch.int32, device=self.device) for w in rank_of}
-        elif self.cfg.codec in ("q8", "sign1"):
-            nbytes = (q8 if self.cfg.codec == "q8" else sign1).payload_bytes(n)
-            slots = {w: torch.empty(nbytes, dtype=torch.uint8, device=self.device) for w in rank_of}
-        else:
-            wire_dtype = torch.float16 if self.cfg.codec == "fp16" else torch.float32
-            slots = {w: torch.empty(n, dtype=wire_dtype, device=self.device) for w in rank_of}
+        own = PC.CODECS[self.cfg.codec]
+        slots = {w: own.slot(n, self.device, self.cfg.topk_ratio) for w in rank_of}
         # one fetch snapshot per worker (codec wire buffers): an in-flight send never races the
         # next update of the arena
         from .codec import FetchCodec
@@ -811,7 +728,7 @@ class ParameterServer:
                         break
                     if kind == "push":
                         res = self.core.on_push(wid, ls)
-                        self.bytes_pushed += _wire_bytes(grads, n)
+                        self.bytes_pushed += self.codec_of(grads).wire_bytes(grads, n)
                         if res.apply:
                             self.apply(grads, res.weight, wid)
                             if box.get("bufs") is not None:

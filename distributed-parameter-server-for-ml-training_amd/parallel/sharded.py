@@ -30,6 +30,7 @@ from __future__ import annotations
 
 import torch
 
+from . import pushcodec
 from .codec import small_index_of
 from .liveness import WatchedRounds
 
@@ -115,7 +116,7 @@ class ShardedSyncChannel(WatchedRounds):
         self.in_place = in_place and not f32
         r = self.rank
         self.lo, self.hi = self.plan.lo[r], self.plan.hi[r]
-        dt = torch.float16 if cfg.codec == "fp16" else torch.float32
+        dt = pushcodec.CODECS[cfg.codec].wire_dtype
         # chunk r of every other rank's wire (all-to-all); this rank's own chunk stays in place
         self.recv = {p: torch.zeros(self.plan.chunk, dtype=dt, device=device) for p in range(self.world) if p != r}
         server.wire = None  # this rank's image range is written by apply_shard, not server.apply
@@ -143,7 +144,7 @@ class ShardedSyncChannel(WatchedRounds):
         return self.server.core.global_step if self.rank == 0 else self._gs
 
     def _push(self, worker_id, grads, local_step, buffers=None):
-        if grads.dtype == torch.int32 or buffers is not None:
+        if pushcodec.is_payload(grads) or buffers is not None:
             raise RuntimeError("the sharded server takes dense gradients without --bn-sync")
         if grads.numel() < self.plan.padded:
             raise RuntimeError("gradient buffer not padded to the shard plan (bind_compute)")

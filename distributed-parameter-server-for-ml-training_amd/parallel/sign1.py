@@ -32,29 +32,24 @@ A block holding a NaN or an Inf sends ``scale = NaN`` and all bits 0 (its residu
 for the whole block): the server's parameters go NaN as with the fp16 wire. Decode-and-sum over
 sources is ``s = 0; s = s + deq_k`` in source order.
 
-Blocks are independent, so every function takes a 256-aligned element sub-range ``off, cnt``.
+Blocks are independent, so every function takes a 256-aligned element sub-range ``off, cnt``. The
+payload's frame is parallel/blockwire.py's; here are the sign coder, its inverse and the body's layout.
 """
 from __future__ import annotations
 
+import sys
+
 import torch
 
-BLOCK = 256
+from . import blockwire as BW
+from .blockwire import BLOCK, num_blocks
+
 MAGIC = 0x31423153  # the bytes 'S' '1' 'B' '1'
-_FMAX = torch.finfo(torch.float32).max
-
-
-def _pad16(x: int) -> int:
-    return (x + 15) & ~15
-
-
-def num_blocks(n: int) -> int:
-    return (n + BLOCK - 1) // BLOCK
 
 
 def section_offsets(n: int):
     """(byte offset of the scales, byte offset of the sign words, payload bytes)."""
-    w_off = 16 + _pad16(4 * num_blocks(n))
-    return 16, w_off, w_off + 32 * num_blocks(n)
+    return BW.section_offsets(n, 32 * num_blocks(n))
 
 
 def payload_bytes(n: int) -> int:
@@ -63,55 +58,24 @@ def payload_bytes(n: int) -> int:
 
 def views(payload: torch.Tensor, n: int):
     """(header int32[4], scales fp32[nblk], sign words int64[4 nblk]) views of a payload."""
-    s_off, w_off, total = section_offsets(n)
-    assert payload.dtype == torch.uint8 and payload.numel() == total, "not a sign1 payload of this n"
-    return (payload[:16].view(torch.int32), payload[s_off:s_off + 4 * num_blocks(n)].view(torch.float32),
-            payload[w_off:total].view(torch.int64))
+    hdr, scales, body = BW.sections(payload, n, 32 * num_blocks(n), "sign1")
+    return hdr, scales, body.view(torch.int64)
 
 
 def empty_payload(n: int, device) -> torch.Tensor:
-    """An all-zero payload with a header (decodes to zeros): a fresh encoder's buffer, and the
-    dedicated server rank's slot in the gather."""
-    p = torch.zeros(payload_bytes(n), dtype=torch.uint8, device=device)
-    p[:16].view(torch.int32).copy_(torch.tensor([MAGIC, n, BLOCK, num_blocks(n)], dtype=torch.int32))
-    return p
-
-
-def _range(n: int, off: int, cnt):
-    cnt = n - off if cnt is None else cnt
-    if off % BLOCK or off < 0 or off + cnt > n or ((off + cnt) % BLOCK and off + cnt != n):
-        raise ValueError("sign1 sub-range: 256-aligned start, end on a block boundary or at n")
-    return off, cnt
-
-
-def _blocks(flat: torch.Tensor) -> torch.Tensor:
-    """[nb, 256] view of a flat fp32 range, the tail block zero-filled."""
-    nb = num_blocks(flat.numel())
-    if nb * BLOCK != flat.numel():
-        flat = torch.cat([flat, flat.new_zeros(nb * BLOCK - flat.numel())])
-    return flat.view(nb, BLOCK)
+    """An all-zero payload with a header (decodes to zeros)."""
+    return BW.empty_payload(MAGIC, payload_bytes(n), n, device)
 
 
 _LANES = torch.arange(64, dtype=torch.int64)
 
 
-def encode_into(g: torch.Tensor, resid: torch.Tensor, payload: torch.Tensor, n: int, off: int = 0, cnt=None):
-    """Encode (resid + g)[off:off+cnt] into ``payload`` and leave resid = acc - deq there."""
-    off, cnt = _range(n, off, cnt)
-    if resid.device.type == "cuda":
-        from ..ops import kernels as K
-
-        K.sign1_encode(g, resid, payload, n, off, cnt)
-        return payload
-    hdr, scales, words = views(payload, n)
-    if off == 0:
-        hdr.copy_(torch.tensor([MAGIC, n, BLOCK, num_blocks(n)], dtype=torch.int32))
-    if cnt == 0:
-        return payload
-    acc = _blocks(resid[off:off + cnt] + g[off:off + cnt].to(torch.float32))
+def quantise(acc: torch.Tensor, cnt: int):
+    """[nb, 256] fp32 blocks holding cnt elements -> (scale [nb], bit [nb, 256], deq [nb, 256]),
+    by the arithmetic of the module docstring."""
     nb = acc.shape[0]
     a = acc.abs()
-    bad = (~(a <= _FMAX)).any(dim=1)  # NaN or Inf
+    bad = BW.nonfinite(a).any(dim=1)
     a4 = a.view(nb, 64, 4)
     t = ((a4[:, :, 0] + a4[:, :, 1]) + a4[:, :, 2]) + a4[:, :, 3]
     w = 32
@@ -123,9 +87,26 @@ def encode_into(g: torch.Tensor, resid: torch.Tensor, payload: torch.Tensor, n: 
         count[-1] = float(cnt % BLOCK)
     scale = torch.where(bad, torch.full_like(count, float("nan")), t[:, 0] / count)
     bit = (acc < 0) & ~bad[:, None]
-    deq = torch.where(bit, -scale[:, None], scale[:, None])
-    res = acc - deq
-    resid[off:off + cnt] = res.view(-1)[:cnt]
+    return scale, bit, torch.where(bit, -scale[:, None], scale[:, None])
+
+
+def encode_into(g: torch.Tensor, resid: torch.Tensor, payload: torch.Tensor, n: int, off: int = 0, cnt=None):
+    """Encode (resid + g)[off:off+cnt] into ``payload`` and leave resid = acc - deq there."""
+    off, cnt = BW.check_range("sign1", n, off, cnt)
+    if resid.device.type == "cuda":
+        from ..ops import kernels as K
+
+        K.sign1_encode(g, resid, payload, n, off, cnt)
+        return payload
+    _, scales, words = views(payload, n)
+    if off == 0:
+        BW.write_header(payload, MAGIC, n)
+    if cnt == 0:
+        return payload
+    acc = BW.blocks(resid[off:off + cnt] + g[off:off + cnt].to(torch.float32))
+    nb = acc.shape[0]
+    scale, bit, deq = quantise(acc, cnt)
+    resid[off:off + cnt] = (acc - deq).view(-1)[:cnt]
     # word j of a block: bit l = sign of element 4 l + j (distinct bits: the sum is their or)
     wd = (bit.view(nb, 64, 4).to(torch.int64) << _LANES[None, :, None]).sum(dim=1)
     b0 = off // BLOCK
@@ -137,7 +118,7 @@ def encode_into(g: torch.Tensor, resid: torch.Tensor, payload: torch.Tensor, n: 
 def decode(payload: torch.Tensor, n: int, out: torch.Tensor | None = None, scale: float = 1.0, add: bool = False,
            off: int = 0, cnt=None) -> torch.Tensor:
     """out[off:off+cnt] = [out +] scale * deq(payload); ``out`` defaults to a new zero tensor."""
-    off, cnt = _range(n, off, cnt)
+    off, cnt = BW.check_range("sign1", n, off, cnt)
     if out is None:
         out = torch.zeros(n, dtype=torch.float32, device=payload.device)
     if payload.device.type == "cuda":
@@ -152,27 +133,8 @@ def decode(payload: torch.Tensor, n: int, out: torch.Tensor | None = None, scale
     bit = ((words[4 * b0:4 * (b0 + nb)].view(nb, 1, 4) >> _LANES[None, :, None]) & 1).bool()
     sc = scales[b0:b0 + nb].view(nb, 1, 1)
     deq = torch.where(bit, -sc, sc).reshape(-1)[:cnt]
-    v = deq * torch.tensor(scale, dtype=torch.float32)
-    dst = out[off:off + cnt]
-    if add:
-        dst.add_(v)
-    else:
-        dst.copy_(v)
-    return out
+    return BW.store(out, off, cnt, deq, scale, add)
 
 
-class Sign1Codec:
-    """Worker-side encoder: owns the error-feedback residual and the payload buffer."""
-
-    def __init__(self, n: int, device="cpu"):
-        self.n = n
-        self.device = torch.device(device)
-        self.payload = empty_payload(n, self.device)
-        self.resid = torch.zeros(n, dtype=torch.float32, device=self.device)
-
-    @property
-    def nbytes(self) -> int:
-        return self.payload.numel()
-
-    def encode(self, g: torch.Tensor) -> torch.Tensor:
-        return encode_into(g[: self.n], self.resid, self.payload, self.n)
+class Sign1Codec(BW.Encoder):
+    wire = sys.modules[__name__]

@@ -31,6 +31,7 @@ import torch
 from ..utils import metrics as M
 from ..utils.data import EpochSampler, shard_range
 from . import control as CP
+from . import pushcodec
 from .liveness import WatchedRounds
 
 
@@ -243,11 +244,11 @@ class SyncCollectiveChannel(WatchedRounds):
         return self._gs
 
     def _push(self, worker_id, grads, local_step, buffers=None):
-        sparse = grads.dtype == torch.int32  # top-k payloads cannot be summed by a reduce: gather
-        q8w = grads.dtype == torch.uint8     # nor can q8 / sign1 payloads (a scale per block and source)
+        # payloads (top-k indices; q8 / sign1: a scale per block and source) cannot be reduced: gathered
+        payload = pushcodec.is_payload(grads)
         world = getattr(self.t, "world_size", 1)
-        dense_gather = not sparse and not q8w and self.agg_mode == "gather" and world > 1
-        if sparse or q8w:
+        dense_gather = not payload and self.agg_mode == "gather" and world > 1
+        if payload:
             gathered = self.t.gather_to_server(grads)
         elif dense_gather:
             if self.server is not None and self._gbufs is None:
@@ -259,16 +260,16 @@ class SyncCollectiveChannel(WatchedRounds):
             self.t.reduce_sum_to_server(buffers)
         if self.server is not None:
             steps = [local_step] * len(self.members)
-            if sparse:
-                self.server.apply_gathered(gathered, self.members, steps, buffers_sum=buffers)
-            elif q8w:  # a dedicated server's own slot is the empty payload: dropped here
-                srcs = gathered if self.root_worker else gathered[1:]
-                self.server.apply_payload_sources(srcs, self.members, steps, buffers_sum=buffers)
+            if payload:
+                # a dedicated server's own slot is the empty payload: an in-kernel decode drops it
+                # here, a top-k round decodes it to nothing
+                drop = not self.root_worker and self.server.codec_of(grads).in_kernel is not None
+                self.server.apply_round(gathered[1:] if drop else gathered, self.members, steps, buffers)
             elif dense_gather:
                 srcs = ([grads] if self.root_worker else []) + [self._gbufs[r] for r in sorted(self._gbufs)]
-                self.server.apply_sources(srcs, self.members, steps, buffers_sum=buffers)
+                self.server.apply_round(srcs, self.members, steps, buffers)
             else:
-                self.server.apply_reduced(grads, self.members, steps, buffers_sum=buffers)
+                self.server.apply_round([grads], self.members, steps, buffers, summed=True)
             self.server.maybe_checkpoint()
         else:
             self._gs = getattr(self, "_gs", 0) + 1
@@ -367,19 +368,8 @@ class Worker:
         # the error-feedback encoder of the push codec (owns the residual and the payload buffer):
         # top-k (parallel/topk.py), block-scaled int8 (parallel/q8.py) or 1-bit sign
         # (parallel/sign1.py); None = dense wire
-        self.encoder = None
-        if cfg.codec == "topk":
-            from .topk import TopKCodec
-
-            self.encoder = TopKCodec(compute.layout.param_numel, cfg.topk_ratio, getattr(compute, "device", "cpu"))
-        elif cfg.codec == "q8":
-            from .q8 import Q8Codec
-
-            self.encoder = Q8Codec(compute.layout.param_numel, getattr(compute, "device", "cpu"))
-        elif cfg.codec == "sign1":
-            from .sign1 import Sign1Codec
-
-            self.encoder = Sign1Codec(compute.layout.param_numel, getattr(compute, "device", "cpu"))
+        self.encoder = pushcodec.CODECS[cfg.codec].encoder(compute.layout.param_numel,
+                                                           getattr(compute, "device", "cpu"), cfg.topk_ratio)
 
     # ---------------------------------------------------------------- reference API
     def connect_to_server(self):

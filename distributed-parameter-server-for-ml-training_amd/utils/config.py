@@ -32,6 +32,13 @@ def _env(name, default, cast=str):
     return cast(v) if v not in (None, "") else default
 
 
+def _push_codecs() -> dict:
+    """The table of push codecs, keyed by the --codec values (parallel/pushcodec.py)."""
+    from ..parallel.pushcodec import CODECS
+
+    return CODECS
+
+
 @dataclass
 class PSConfig:
     # --- reference server flags
@@ -155,7 +162,7 @@ class PSConfig:
             raise ValueError("Number of workers must be between 1 and 32")
         if self.eval_workers not in ("all", "first"):
             raise ValueError("--eval-workers must be all or first")
-        if self.codec not in ("none", "fp16", "q8", "sign1", "topk"):
+        if self.codec not in _push_codecs():
             raise ValueError(f"--codec must be none, fp16, q8, sign1 or topk, got {self.codec!r}")
         if self.topology not in ("colocated", "dedicated", "sharded"):
             raise ValueError(f"--topology must be colocated, dedicated or sharded, got {self.topology!r}")
@@ -279,7 +286,7 @@ class PSConfig:
     @property
     def dense_wire(self) -> bool:
         """The push is the dense gradient buffer itself (fp16 cast or fp32), not an encoded payload."""
-        return self.codec in ("fp16", "none")
+        return _push_codecs()[self.codec].reducible
 
     def to_json(self) -> str:
         return json.dumps(dataclasses.asdict(self), sort_keys=True)
@@ -305,7 +312,7 @@ def add_arguments(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
     A("--num-classes", type=int, default=None)
     A("--gpus", "--nproc", dest="gpus", type=int, default=None)
     A("--topology", choices=["colocated", "dedicated", "sharded"], default=None)
-    A("--codec", choices=["none", "fp16", "q8", "sign1", "topk"], default=None,
+    A("--codec", choices=list(_push_codecs()), default=None,
       help="gradient wire: fp16 cast (reference, default), none (fp32), q8 (block-scaled int8, 1.016 B/param), "
            "sign1 (1-bit sign + a scale per 256, 0.1406 B/param) or topk; q8, sign1 and topk keep an error-feedback "
            "residual on the worker")

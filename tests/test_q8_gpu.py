@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from psx.ops import kernels as K
+from psx.ops._lib import HipError
 from psx.parallel import q8 as Q
 
 from .test_q8_cpu import check_step, make_grads
@@ -99,6 +100,30 @@ def _payloads(n: int, W: int):
 
 
 _payloads.cache = {}
+
+
+def test_payload_over_the_state_is_refused():
+    """A payload that shares a byte with what the call writes is refused with hipErrorInvalidValue
+    before anything is launched: q8_apply_multi with a payload that is a view of p's own storage,
+    q8_decode with dst over the payload (n = 257). p and dst keep their bits."""
+    n = 257
+    pb = Q.payload_bytes(n)
+    payload = Q.Q8Codec(n).encode(make_grads(n, torch.float32, steps=1, seed=3)[0])
+    p = torch.randn(n, device=DEV)
+    inside = p.view(torch.uint8)[:pb]
+    inside.copy_(payload.to(DEV))
+    before = p.clone()
+    with pytest.raises(HipError, match="q8_apply_multi failed with code 1$"):
+        K.q8_apply_multi(p, [inside], 0.1, n=n)
+    torch.cuda.synchronize()
+    assert _same(p, before)
+    store = torch.zeros(4 * n, dtype=torch.uint8, device=DEV)
+    store[:pb] = payload.to(DEV)
+    dst, before = store.view(torch.float32), store.clone()
+    with pytest.raises(HipError, match="q8_decode failed with code 1$"):
+        K.q8_decode(store[:pb], dst, n)
+    torch.cuda.synchronize()
+    assert torch.equal(store, before)
 
 
 @pytest.mark.parametrize("n", [257, 4097, 1_000_003])

@@ -141,7 +141,7 @@ def _payloads(n, wires, kind, device):
 
 
 ROUTES = ("apply", "apply_range", "apply_range_sources", "apply_sources", "apply_reduced", "apply_gathered",
-          "apply_q8_sources", "_apply_q8", "push_gradients")
+          "apply_payload_sources", "_apply_payloads", "push_gradients")
 
 
 def check_every_route_updates(rule, device):
@@ -167,10 +167,10 @@ def check_every_route_updates(rule, device):
             assert s.apply_reduced(sum(wires).to(device), members, steps)
         elif route == "apply_gathered":
             assert s.apply_gathered(_payloads(n, wires, "topk", device), members, steps)
-        elif route == "apply_q8_sources":
-            assert s.apply_q8_sources(_payloads(n, wires, "q8", device), members, steps)
-        elif route == "_apply_q8":
-            s._apply_q8(_payloads(n, wires, "q8", device), 1.0 / W)
+        elif route == "apply_payload_sources":
+            assert s.apply_payload_sources(_payloads(n, wires, "q8", device), members, steps)
+        elif route == "_apply_payloads":
+            s._apply_payloads(_payloads(n, wires, "q8", device), 1.0 / W)
             s.finish_round_apply()
         else:
             for w in members:
