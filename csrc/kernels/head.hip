@@ -374,11 +374,16 @@ using namespace psx;
 
 namespace {
 
+// the split path of a large head (pool + GEMM + softmax launches; no BN-backward sums)
+bool head_split(int C, int K, bool bufs) { return (long)K * C > (1L << 18) && C % 64 == 0 && bufs; }
+// the fused per-sample head's refusal
+bool head_fused_ok(int C, int K) { return !(K > 1024 || C % 16 || (C > 512 && C % 512)); }
+
 template <typename T>
 int head_fwd_bwd_t(const void* act, int B, int HW, int C, const float* fcw, const float* fcb, int K,
                    const int* labels, float* pooled, float* dlogits, void* dact, float* loss, int* correct,
                    const HeadBnStats* bst, hipStream_t st) {
-  if ((long)K * C > (1L << 18) && C % 64 == 0 && pooled && dlogits) {  // large head: split path
+  if (head_split(C, K, pooled && dlogits)) {  // large head: split path
     hipLaunchKernelGGL(head_pool_kernel<T>, dim3(B, (C + 511) / 512), dim3(256), 0, st, (const T*)act, HW, C,
                        pooled, dlogits, (long)B * K);
     // logits: split-K over the C-long dot products (a 2048 x 1000 head at B = 128 is only 64
@@ -394,7 +399,7 @@ int head_fwd_bwd_t(const void* act, int B, int HW, int C, const float* fcw, cons
     const int e = (int)hipGetLastError();
     return e ? -e : 0;
   }
-  if (K > 1024 || C % 16 || (C > 512 && C % 512)) return -2;
+  if (!head_fused_ok(C, K)) return -2;
   // >= 16 + 1024 bytes: the deterministic-mode reduction's flag + scratch (bnfin.hpp det_finish)
   const size_t lds = std::max<size_t>((size_t)(C + K + 64) * sizeof(float), 1040);
   const HeadBnStats bs = (bst && dact) ? *bst : HeadBnStats{};
@@ -412,6 +417,10 @@ int head_fwd_bwd_t(const void* act, int B, int HW, int C, const float* fcw, cons
 }  // namespace
 
 extern "C" {
+
+// Whether psx_head_fwd_bwd, given bst and dact (and pooled, dlogits), produces the BN-backward
+// sums (returns 1), on the host alone: the fused per-sample head runs and accepts the shape.
+int psx_head_sums_ok(int C, int K) { return !head_split(C, K, true) && head_fused_ok(C, K); }
 
 // bst (nullable, fused path only, needs dact): the BN-backward sums of the consumed layer.
 // Returns 1 when they were produced (the caller then skips its bn_bwd_reduce), 0 otherwise.

@@ -433,9 +433,14 @@ extern "C" {
 // statistics [PSX_STAT_SLOTS][2][64] (nullable) of (y - sshift) (sshift nullable). x: NHWC with
 // cp = one 16-byte chunk of channels (4 fp32 / 8 bf16, zero padded); wf: the conv_v2 forward
 // weights [64][Kg], k = tap * cp + c. -11: not this shape (the caller runs psx_conv_fwd2 instead).
+// psx_stem_conv's shape test on the host alone (the entry's own first lines): 1 = it launches.
+int psx_stem_ok(int W, int cin, int cp, int OC, int Kg, int f32) {
+  return !(cin != 3 || OC != 64 || cp != (f32 ? 4 : 8) || Kg < 9 * cp || W % 4);
+}
+
 int psx_stem_conv(const void* x, const void* wf, void* y, float* stats, const float* sshift, int Nb, int H, int W,
                   int cin, int cp, int OC, int Kg, int f32, hipStream_t st) {
-  if (cin != 3 || OC != 64 || cp != (f32 ? 4 : 8) || Kg < 9 * cp || W % 4) return -11;
+  if (!psx_stem_ok(W, cin, cp, OC, Kg, f32)) return -11;
   const long npix = (long)Nb * H * W;
   if (npix <= 0 || npix > (1L << 30)) return -2;
   const dim3 grid((unsigned)((npix + 255) / 256));
@@ -456,9 +461,14 @@ int psx_stem_conv(const void* x, const void* wf, void* y, float* stats, const fl
 // fp32 / 8 bf16 channels, the padding zero); wf: the conv_v2 forward weights [64][Kg],
 // k = tap * cp + c (tap = r * 7 + s), Kg >= 49 cp.
 // The output is 112 x 112 (IH = IW = 224). -11: not this shape (the caller runs psx_conv_fwd2).
+// psx_stem7_conv's shape test on the host alone (the entry's own first lines): 1 = it launches.
+int psx_stem7_ok(int Nb, int IH, int IW, int cin, int cp, int OC, int Kg, int f32) {
+  return !(cin != 3 || cp != (f32 ? 4 : 8) || OC != 64 || Kg < 49 * cp || IH != 224 || IW != 224 || Nb < 1);
+}
+
 int psx_stem7_conv(const void* x, const void* wf, void* y, float* stats, const float* sshift, int Nb, int IH,
                    int IW, int cin, int cp, int OC, int Kg, int f32, hipStream_t st) {
-  if (cin != 3 || cp != (f32 ? 4 : 8) || OC != 64 || Kg < 49 * cp || IH != 224 || IW != 224 || Nb < 1) return -11;
+  if (!psx_stem7_ok(Nb, IH, IW, cin, cp, OC, Kg, f32)) return -11;
   const unsigned grid = (unsigned)Nb * (kS7W / kS7Rows);
   const DetRed det = stats ? det_for(stats) : DetRed{};
   if (f32)

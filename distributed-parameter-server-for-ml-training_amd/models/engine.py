@@ -24,136 +24,20 @@ The network is described by a generic block list so ResNet-18 (CIFAR stem) and R
 from __future__ import annotations
 
 import contextlib
-import os
-from dataclasses import dataclass, field
+from dataclasses import replace
 
 import numpy as np
 import torch
 
 from ..ops import kernels as K
-from ..utils.tune import tune, tune_flag
 from .layout import ParamLayout
-from .resnet import Bottleneck, BasicBlock
+from .plan import BNSpec, ConvSpec, EngineOptions, all_bns, all_convs, netspec_from_module, plan_step
 
 CIFAR_MEAN = (0.5071, 0.4867, 0.4408)  # reference worker.py:149-150
 CIFAR_STD = (0.2675, 0.2565, 0.2761)
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
-
-
-def _pow2_ceil(v: int, lo: int = 8) -> int:
-    p = lo
-    while p < v:
-        p *= 2
-    return p
-
-
-@dataclass
-class ConvSpec:
-    name: str
-    cin: int
-    cout: int
-    k: int
-    stride: int
-    pad: int
-    h: int = 0  # input spatial
-    w: int = 0
-    need_dgrad: bool = True
-    cp: int = 0
-    kg: int = 0
-    kgd: int = 0
-    wf_off: int = 0
-    wd_off: int = -1
-
-    def finalize(self, chunk: int = 8):
-        # input channels padded to a power of two >= one 16-byte chunk (8 bf16 / 4 fp32)
-        self.cp = _pow2_ceil(self.cin, chunk)
-        self.kg = -(-(self.k * self.k * self.cp) // 64) * 64
-        self.kgd = self.k * self.k * self.cout  # cout % 64 == 0 for every ResNet conv
-        assert self.kgd % 64 == 0 and self.cout % 64 == 0, self.name
-
-    @property
-    def out_hw(self):
-        return K.conv_out_hw(self.h, self.w, self.k, self.stride, self.pad)
-
-
-@dataclass
-class BNSpec:
-    name: str
-    c: int
-
-
-@dataclass
-class BlockSpec:
-    convs: list
-    bns: list
-    down: tuple | None = None  # (ConvSpec, BNSpec)
-
-
-@dataclass
-class NetSpec:
-    stem_conv: ConvSpec
-    stem_bn: BNSpec
-    maxpool: bool
-    blocks: list = field(default_factory=list)
-    fc: str = "fc"
-    fc_in: int = 512
-    classes: int = 100
-    in_hw: tuple = (32, 32)
-
-
-def netspec_from_module(model: torch.nn.Module, in_hw) -> NetSpec:
-    def conv_of(m, name, h, w):
-        return ConvSpec(name, m.in_channels, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0], h, w)
-
-    h, w = in_hw
-    stem = conv_of(model.conv1, "conv1", h, w)
-    stem.need_dgrad = False
-    h, w = stem.out_hw
-    maxpool = hasattr(model, "maxpool")
-    if maxpool:
-        h, w = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-    spec = NetSpec(stem, BNSpec("bn1", model.bn1.num_features), maxpool)
-    for li in range(1, 5):
-        layer = getattr(model, f"layer{li}")
-        for bi, blk in enumerate(layer):
-            pre = f"layer{li}.{bi}"
-            if isinstance(blk, BasicBlock):
-                names = ["conv1", "conv2"]
-                down_mod = blk.shortcut if len(blk.shortcut) else None
-                down_names = (f"{pre}.shortcut.0", f"{pre}.shortcut.1")
-            elif isinstance(blk, Bottleneck):
-                names = ["conv1", "conv2", "conv3"]
-                down_mod = blk.downsample
-                down_names = (f"{pre}.downsample.0", f"{pre}.downsample.1")
-            else:
-                raise TypeError(type(blk))
-            convs, bns = [], []
-            ch, cw = h, w
-            for i, n in enumerate(names):
-                m = getattr(blk, n)
-                cs = conv_of(m, f"{pre}.{n}", ch, cw)
-                convs.append(cs)
-                bns.append(BNSpec(f"{pre}.bn{i + 1}", getattr(blk, f"bn{i + 1}").num_features))
-                ch, cw = cs.out_hw
-            down = None
-            if down_mod is not None:
-                ds = conv_of(down_mod[0], down_names[0], h, w)
-                down = (ds, BNSpec(down_names[1], down_mod[1].num_features))
-            spec.blocks.append(BlockSpec(convs, bns, down))
-            h, w = ch, cw
-    spec.fc_in = model.fc.in_features
-    spec.classes = model.fc.out_features
-    spec.in_hw = tuple(in_hw)
-    return spec
-
-
-def all_convs(spec: NetSpec):
-    yield spec.stem_conv
-    for b in spec.blocks:
-        yield from b.convs
-        if b.down:
-            yield b.down[0]
+_BN_PARAMS = ("weight", "bias", "running_mean", "running_var")
 
 
 class HipResNetEngine:
@@ -161,14 +45,14 @@ class HipResNetEngine:
 
     def __init__(self, model: torch.nn.Module, layout: ParamLayout, batch: int, device="cuda",
                  grad_dtype=torch.float16, in_hw=(32, 32), mean=CIFAR_MEAN, std=CIFAR_STD, bn_eps=1e-5,
-                 bn_momentum=0.1, seed=1234, dtype=torch.bfloat16, deterministic=None):
+                 bn_momentum=0.1, seed=1234, dtype=torch.bfloat16, deterministic=None,
+                 options: EngineOptions | None = None):
         if not torch.cuda.is_available():
             raise RuntimeError("HipResNetEngine needs an MI355X (torch.cuda / HIP device)")
         K.unpack_desc_size()  # fail loudly right here if the native library is missing
         self.dev = torch.device(device)
         self.layout = layout
         self.B = batch
-        self.spec = netspec_from_module(model, in_hw)
         self.grad_dtype = grad_dtype
         self.grad_fp16 = grad_dtype == torch.float16
         # compute dtype of activations and conv operands (fp32 = the reference's precision)
@@ -176,67 +60,33 @@ class HipResNetEngine:
             raise ValueError(f"engine dtype {dtype}: bfloat16 or float32")
         self.dtype = dtype
         self.f32 = dtype == torch.float32
-        # deterministic mode (the default; PSX_DETERMINISTIC=0 or deterministic=False: off): every
-        # BN statistic accumulates as exact fixed-point integers (csrc/kernels/bnfin.hpp DetRed),
-        # so two runs of a step give bit-identical gradients, for +0-2 % step time
-        if deterministic is None:
-            deterministic = os.environ.get("PSX_DETERMINISTIC", "1") == "1"
-        self.deterministic = bool(deterministic)
+        self.spec = netspec_from_module(model, in_hw, self.f32)
+        # the options (models/plan.py EngineOptions; default: PSX_TUNE / PSX_DETERMINISTIC) and the
+        # step plan made from them are fixed for the engine's life
+        if options is None:
+            options = EngineOptions.from_env(self.f32, in_hw, deterministic)
+        elif deterministic is not None:
+            options = replace(options, deterministic=bool(deterministic))
+        self.opts = options
+        self.deterministic = options.deterministic
+        self.plan = plan_step(self.spec, batch, self.f32, options)
         self.mean, self.std = mean, std
         self.eps, self.mom = bn_eps, bn_momentum
         self.seed = seed
         self.graph = None
         self.graphs = None
         self.segments = None  # backward split points (set_segments), None = one segment
-        # BN finalize inside the producing launch (csrc/kernels/bnfin.hpp): off (tests switch the
-        # attribute: tests/test_engine_gpu.py)
-        self.fuse_fin = False
-        # BN-backward sums from the dgrad epilogue (skips the separate bn_bwd_reduce pass where a
-        # dgrad produces the BN's input gradient): neutral with 32 stat slots + separate finalize
-        # (2.215 vs 2.217 ms/step), a small win with 8 slots + folded finalize (1.996/2.000 vs
-        # 2.010/2.006 ms/step, two same-box A/B pairs), so on (the attribute is a test switch)
-        # BN finalize folded into the consuming apply launches (bnfin.hpp bn_fin_lds): every apply
-        # workgroup re-derives the affine/coefficients from the stat slots, removing 40 finalize
-        # launches per step. With 32 slot rows it measured slower (2.18 vs 2.10 ms/step); with 8
-        # rows (csrc/kernels/common.hpp) it wins: 1.999 vs 2.019 ms/step.
-        self.fin_apply = not self.fuse_fin
-        self.fuse_bnbwd = True
-        self._prereduced = set()
-        # with the fused sums the dgrad epilogue already reads the ReLU mask operand o: it stores
-        # dz = g*[o > 0] instead of g (bwd_stats_desc mask_store), the BN-backward apply then runs
-        # without o (one activation read less per BN layer) and dz doubles as the identity
-        # shortcut's gradient (no dzout copy)
-        self.mask_store = self.fuse_bnbwd
-        # BN-backward applies folded into the fused Winograd data gradient + dy transform (_bn_bwd_to)
-        self.bwd_fold = self.mask_store and tune_flag("wino_bwdfold", True)
-        self._bwd_fold = {}
-        self._premasked = set()
-        # weight gradients (+ their batched reductions) on a side stream, a parallel branch of the
-        # captured step graph next to the dgrad -> BN-backward chain. PSX_TUNE wgrad_stream=1 / 0
-        # forces it; the default keeps it except for the fp32 engine on CIFAR-size images, whose
-        # fused Winograd weight gradients (1 workgroup per CU, like the data gradients beside them)
-        # only time-share the chip with the dgrad chain and add cross-queue waits: same box
-        # 3.35-3.38 -> 3.28-3.29 ms/step without it (r4_call20/21); bf16 ResNet-18 (1.85 -> 1.89)
-        # and fp32 ResNet-50 (40.4 -> 41.5) keep it.
-        ws = tune("wgrad_stream", "auto")
-        if ws == "auto":
-            ws = "0" if (self.f32 and max(self.spec.in_hw) <= 64) else "1"
-        self.wg_stream = torch.cuda.Stream(device=self.dev) if ws == "1" else None
-        # the stride-2 block's 1x1 shortcut data gradient folded into the 3x3 one's launch
-        self.fold_sc = True
-        # the CIFAR stem on the direct vector-ALU kernel (csrc/kernels/stem.hip): fp32 27.4 -> 19.5 us
-        # in isolation (bench/stem_probe.py); step A/B within noise, bf16 unmeasured in isolation.
-        # The direct stems: fp32 (CIFAR 3x3 and ImageNet 7x7) and the bf16 ImageNet 7x7 (stem.hip)
-        self.stem_direct = self.f32 or self.spec.stem_conv.k == 7
-        # the later stages' Winograd weight transforms overlap the first stage's forward on the
-        # side stream; without one they stay on the compute stream (a stream of their own measured
-        # 3.36 vs 3.28 ms/step — a forked branch at the step start costs more than the overlap
-        # returns, r4_numbers.jsonl r4_call23 — and was removed)
-        self.wt_stream = self.wg_stream
-        self._wg_batch = None
+        # the side stream of the weight gradients and the late Winograd weight transforms
+        self.wg_stream = torch.cuda.Stream(device=self.dev) if self.plan.wgrad_stream else None
+        self._wg_batch = self._wr_batch = None  # issue queues of one backward unit (_bwd_block)
+        self._late_ev = None
+        self._wino_wb_key = None
+        self._zeroed = False       # red zeroed by this step's augment launch (consumed by forward)
+        self._zeroed_head = False  # correct zeroed by it (consumed by head)
         self._fins = {}
         self.wsrc = None        # bf16 weight image to unpack from (set_weight_source), None = arena
         self.pre_unpack = None
+        self.small_scatter = None
         self._build()
 
     def _set_unpack_descs(self, convs):
@@ -245,7 +95,8 @@ class HipResNetEngine:
         descs = []
         tile0 = 0  # flat grid of param_unpack_tiles: (64x64 (oc, c) tile, chunk of <= 3 taps) units
         for cs in convs:
-            descs.append((self.layout.offset(f"{cs.name}.weight"), cs.wf_off, cs.wd_off, cs.cout, cs.cin, cs.k, cs.k,
+            p = self.plan.convs[cs.name]
+            descs.append((self.layout.offset(f"{cs.name}.weight"), p.wf_off, p.wd_off, cs.cout, cs.cin, cs.k, cs.k,
                           cs.cp, cs.kg, cs.kgd, tile0))
             tile0 += -(-cs.cout // 64) * -(-cs.cp // 64) * -(-(cs.k * cs.k) // 3)
         self.ntiles = tile0
@@ -267,20 +118,12 @@ class HipResNetEngine:
         return torch.zeros(*shape, dtype=torch.float32, device=self.dev)
 
     def _build(self):
-        sp, B = self.spec, self.B
-        # weights: one bf16 buffer holding every conv's fwd (and dgrad) operand
-        off = 0
-        for cs in all_convs(sp):
-            cs.finalize(4 if self.f32 else 8)
-            cs.wf_off = off
-            off += cs.cout * cs.kg
-            if cs.need_dgrad:
-                cs.wd_off = off
-                off += cs.cp * cs.kgd
-            else:
-                cs.wd_off = -1
-        self.wbuf = torch.zeros(off, dtype=self.dtype, device=self.dev)
-        self._set_unpack_descs(list(all_convs(sp)))
+        sp, B, plan = self.spec, self.B, self.plan
+        # weights: one buffer of the compute dtype holding every conv's fwd (and dgrad) operand.
+        # Winograd layers read their own transformed weights (unpack -> _wino_unpack): they are not
+        # in the implicit-GEMM operand unpack (13 of ResNet-18's 20 convs, most bytes)
+        self.wbuf = torch.zeros(plan.wbuf, dtype=self.dtype, device=self.dev)
+        self._set_unpack_descs([cs for cs in all_convs(sp) if not plan.convs[cs.name].wino])
 
         H, W = sp.in_hw
         self.x0 = self._bf(B, H, W, sp.stem_conv.cp)
@@ -290,42 +133,23 @@ class HipResNetEngine:
         self.index = self.batch_meta[:B]
         self.step_dev = self.batch_meta[B:]
 
-        # per-BN persistent state: affine [2,C] (scale, shift), saved [2,C] (mean, invstd), coef [3,C]
-        self.bn = {}
-
         # Cross-workgroup reductions (BN fwd statistics from the conv epilogue, BN bwd sums) use
         # fp32 atomics into PSX_STAT_SLOTS slot rows per BN layer; all slot rows live in one
         # buffer that is zeroed once at the start of every step (one memset node in the graph).
-        self.nslots = K.bn_bwd_reduce_T(1, 64)
+        self.nslots = plan.nslots
+        self.red = self._f32(plan.red_len)
         # BN statistic shifts (csrc/kernels/bnfin.hpp BnFin::sshift): the forward statistics are
         # sums of (y - k) and (y - k)^2 with k = the layer's previous batch mean, so the variance
         # never cancels two large numbers when |mean| >> std. Row 0 = this step's k (read-only
         # during the step), row 1 = the batch means the finalizes write; the next training step's
         # augment launch copies row 1 -> row 0. Zero at the first step (plain sums).
-        nshift = sp.stem_bn.c + sum(bs.c for b in sp.blocks for bs in b.bns) + \
-            sum(b.down[1].c for b in sp.blocks if b.down)
-        self.bn_shift = torch.zeros(2, nshift, dtype=torch.float32, device=self.dev)
-        shift_off = [0]
-        # the first CTR words of the slot buffer are the in-launch finalize counters (two per BN
-        # layer: forward, backward; csrc/kernels/bnfin.hpp) — zeroed with the slots every step
-        nbn = 1 + sum(len(b.bns) + (1 if b.down else 0) for b in sp.blocks)
-        self.ctr_words = -(-2 * nbn // 64) * 64
-        red_off = [self.ctr_words]
-        nctr = [0]
-
-        # deterministic mode: every slot entry is a 16-byte fixed-point pair (bnfin.hpp DetRed)
-        sw = K.det_slot_scale() if self.deterministic else 1
-
-        def bn_state(bs: BNSpec):
-            fwd = red_off[0]
-            bwd = fwd + sw * self.nslots * 2 * bs.c
-            red_off[0] = bwd + sw * self.nslots * 3 * bs.c
-            nctr[0] += 2
-            so = shift_off[0]
-            shift_off[0] += bs.c
+        self.bn_shift = torch.zeros(2, plan.nshift, dtype=torch.float32, device=self.dev)
+        # per-BN persistent state: affine [2,C] (scale, shift), saved [2,C] (mean, invstd), coef [3,C]
+        self.bn = {}
+        for bs in all_bns(sp):
+            so = plan.bns[bs.name].shift_off
             self.bn[bs.name] = dict(affine=self._f32(2, bs.c), saved=self._f32(2, bs.c), coef=self._f32(3, bs.c),
-                                    c=bs.c, fwd=(fwd, sw * self.nslots * 2 * bs.c), bwd=(bwd, sw * self.nslots * 3 * bs.c),
-                                    ctr=nctr[0] - 2, sshift=self.bn_shift[0, so:so + bs.c],
+                                    c=bs.c, sshift=self.bn_shift[0, so:so + bs.c],
                                     sshift_next=self.bn_shift[1, so:so + bs.c])
 
         # activation / gradient buffers
@@ -335,24 +159,6 @@ class HipResNetEngine:
         self.a0 = self._bf(B, p, q, st.cout)
         self.g0 = self._bf(B, p, q, st.cout)   # grad wrt a0 (or wrt maxpool input)
         self.dy0 = self._bf(B, p, q, st.cout)
-        bn_state(sp.stem_bn)
-        max_wg = 0
-        max_wp = 0
-
-        def track(cs: ConvSpec):
-            # fp32 scratch: wgrad split-K partials (own buffer: wgrad may run on a side stream)
-            # and conv split-K slabs (stream-ordered on the main stream)
-            nonlocal max_wg, max_wp
-            s = K.conv_wgrad2_splits(B, cs.h, cs.w, cs.cp, cs.cout, cs.k, cs.stride, cs.pad, cs.kg, self.f32)
-            cs.splits = s
-            oh, ow = cs.out_hw
-            cs.wp = s * cs.cout * cs.kg  # fp32 partials of this layer (offset wp_off: _plan_wpart)
-            cs.wp_off = 0
-            max_wp = max(max_wp, cs.wp)
-            max_wg = max(max_wg, K.conv2_workspace_bytes(B, oh, ow, cs.cout, cs.kg, self.f32) // 4,
-                         K.conv2_workspace_bytes(B, cs.h, cs.w, cs.cp, cs.kgd, self.f32) // 4 if cs.need_dgrad else 0)
-
-        track(st)
         h_in = self.a0
         if sp.maxpool:  # ImageNet stem: 3x3/s2 max-pool after bn1+relu (csrc/kernels/pool.hip)
             mh, mw = (p + 2 - 3) // 2 + 1, (q + 2 - 3) // 2 + 1
@@ -360,6 +166,7 @@ class HipResNetEngine:
             self.pidx = torch.empty(B, mh, mw, st.cout, dtype=torch.uint8, device=self.dev)
             h_in = self.p0
         self.blk = []
+        self.xsrc = {}  # conv whose input relu(BN(y)) is never written -> (pre-BN y, BN affine)
         for b in sp.blocks:
             d = dict(inp=h_in)
             d["y"] = [self._bf(B, *cs.out_hw, cs.cout) for cs in b.convs]
@@ -369,14 +176,11 @@ class HipResNetEngine:
             last = b.convs[-1]
             d["out"] = self._bf(B, *last.out_hw, last.cout)
             d["gin"] = torch.empty_like(h_in)  # grad wrt block input
-            for cs in b.convs:
-                track(cs)
-            for bs in b.bns:
-                bn_state(bs)
+            for i, cs in enumerate(b.convs):
+                if plan.convs[cs.name].xfold:
+                    self.xsrc[cs.name] = (d["y"][i - 1], self.bn[b.bns[i - 1].name]["affine"])
             if b.down:
                 ds, dbn = b.down
-                track(ds)
-                bn_state(dbn)
                 d["ys"] = self._bf(B, *ds.out_hw, ds.cout)
                 d["dys"] = self._bf(B, *ds.out_hw, ds.cout)
                 d["dxs"] = torch.empty_like(h_in)
@@ -385,14 +189,27 @@ class HipResNetEngine:
             self.blk.append(d)
             h_in = d["out"]
         self.final = h_in
-        self.red = self._f32(red_off[0])
-        self.wpart = self._f32(max(1, max_wg))
-        self.wpart_w = self._f32(max(1, self._plan_wpart(max_wp)))
-        self._plan_wino()
-        if self.wino_layers:
-            # Winograd layers read their own transformed weights (unpack -> _wino_unpack): drop
-            # them from the implicit-GEMM operand unpack (13 of ResNet-18's 20 convs, most bytes)
-            self._set_unpack_descs([cs for cs in all_convs(sp) if cs.name not in self.wino_layers])
+        # fp32 scratch: conv split-K slabs (stream-ordered on the compute stream) and the weight
+        # gradients' split-K partials (own buffer: they may run on the side stream)
+        self.wpart = self._f32(max(1, plan.wpart))
+        self.wpart_w = self._f32(max(1, plan.wpart_w))
+        # Winograd: per layer (U, U', V | None: the forward's V goes to scratch); compute-stream
+        # scratch (forward V of layers without a Winograd weight gradient / GEMM output;
+        # data-gradient input tiles + GEMM output) and the weight gradients' own (dy tiles, GEMM
+        # partials), once more for the tail weight gradient that runs beside the side stream's
+        self.wu = {}
+        for cs in all_convs(sp):
+            cp = plan.convs[cs.name]
+            if cp.wino:
+                self.wu[cs.name] = (self._f32(cp.uf_rows * cs.cout * cs.cp),
+                                    self._f32(cp.ud_rows * cs.cout * cs.cp) if cp.ud_rows else None,
+                                    self._f32(cp.v_floats) if cp.keep_v else None)
+        if self.wu:
+            self.wino_s1 = self._f32(max(1, plan.s_main))
+            self.wino_s2 = self._f32(max(1, plan.s_main))
+            self.wino_wd = self._f32(max(1, plan.s_d))
+            self.wino_wpart = self._f32(max(1, plan.s_part))
+            self.wino_tail = (self._f32(max(1, plan.s_d)), self._f32(max(1, plan.s_part))) if plan.tail_split else None
         # head
         fh, fw = self.final.shape[1], self.final.shape[2]
         self.head_hw = fh * fw
@@ -404,110 +221,6 @@ class HipResNetEngine:
         # gradient wire buffer (trainable-parameter prefix of the arena)
         self.grads = torch.zeros(self.layout.param_numel, dtype=self.grad_dtype, device=self.dev)
 
-    def _plan_wino(self):
-        """fp32 Winograd F(4x4,3x3) (csrc/kernels/wino.hip) for the 3x3 / stride-1 layers: forward
-        and data gradient on images up to 64x64 (every 3x3 stride-1 layer of
-        ResNet-18 CIFAR and ResNet-50's 56x56 / 28x28 ones; R50 fp32 top-k 3,060 -> 3,188 img/s),
-        weight gradient up to 64x64
-        (default 16: on 32x32 the direct tap-reuse kernel is faster, 101 vs 129 us). Same-box
-        per-layer A/B in profiles/r2s4_wino_*.jsonl. Per layer: the transformed forward weights
-        U [cout][36][cin] and data-gradient weights U' [cin][36][cout] (rebuilt by unpack() every
-        step) and, where the weight gradient is Winograd, the transformed input V [36][T][cin] the
-        forward leaves for it. In deterministic mode its BN sums take the fixed-order reduction
-        like every other producer (wino_out_kernel + bnfin.hpp DetRed). Not for bf16. PSX_TUNE wino=0:
-        direct kernels everywhere. Layers with 64 / 128 input channels (ResNet-18's 32x32 and 16x16
-        stages) run forward and data gradient as ONE fused launch each (wino_fused.hip: the
-        transforms inside the GEMM, V / P never in HBM; the other layers take the three-launch path;
-        bench/wino_fused_ab.py: 32x32x64 fwd / dgrad 80 / 95 -> 58 / 63 us, 16x16x128 59 / 62 -> 50 / 51).
-        The fused forward still writes V where the Winograd weight gradient reads it."""
-        self.wino_layers = {}
-        self.wino_wgrad = set()
-        self.wino_wgf = set()   # weight gradient by the fused kernel (wino_wgrad.hip): reads x, not V
-        self.wino_bnfold = {}
-        self.wino_fused = {}
-        self.wino_dz = set()    # three-launch layers whose backward transforms dz once (wino_dz_xf)
-        self._dz_pre = None
-        self._xfold = {}        # conv -> (pre-BN y, BN affine): its input is relu(BN(y)), never written
-        if not self.f32 or not tune_flag("wino", True):
-            return
-        fuse = True  # the fused single-launch kernel (wino_fused.hip) wherever it applies
-        # fused weight gradient (wino_wgrad.hip) on images of at least 16x16: same box,
-        # B = 128, us incl. output transform, fused vs three-launch (profiles/r4_wino_wgrad_ab.jsonl,
-        # one row per layer): 32x32x64 58.4 vs 71.2, 16x16x128 55.3 vs 46.9 (+ the
-        # forward's V store the three-launch path needs, ~7), 8x8x256 53.7 vs 43.2, 4x4x512 61.7 vs
-        # 44.1. In the step (side stream; the forward's V store is on the critical path) same box:
-        # off 3.568, >= 32 3.412, >= 16 3.363-3.372 ms/step (profiles/r4_numbers.jsonl)
-        wgf, wgf_minhw = True, 16
-        maxhw = 64
-        wg = True
-        # Winograd weight gradient up to 64x64 images: ResNet-50's 56x56 3x3 layers take the fused
-        # one (their direct alternative is wgrad2f: the tap-reuse kernel needs power-of-two rows):
-        # same box 36.8 -> 36.4 ms/step (profiles/r5_numbers.jsonl r5_call6)
-        wg_maxhw = 64
-        B = self.B
-        s_main = s_d = s_part = 0
-        for cs in all_convs(self.spec):
-            if (cs.k != 3 or cs.stride != 1 or cs.pad != 1 or cs.cp != cs.cin or cs.h > maxhw or cs.w > maxhw
-                    or not K.wino_ok(cs.h, cs.w, cs.cp, cs.cout)):
-                continue
-            vk, vc = K.wino_v_floats(B, cs.h, cs.w, cs.cout), K.wino_v_floats(B, cs.h, cs.w, cs.cp)
-            s_main = max(s_main, vk, vc, K.wino_p_floats(B, cs.h, cs.w, cs.cp, cs.cout),
-                         K.wino_p_floats(B, cs.h, cs.w, cs.cout, cs.cp))
-            q = K.wino_wgrad_q(B, cs.h, cs.w, cs.cp, cs.cout) if wg and max(cs.h, cs.w) <= wg_maxhw else 0
-            # fused single-launch kernel (wino_fused.hip) where it applies, per direction
-            ff = fuse and K.wino_fused_ok(B, cs.h, cs.w, cs.cp, cs.cout)
-            fd = fuse and cs.need_dgrad and K.wino_fused_ok(B, cs.h, cs.w, cs.cout, cs.cp)
-            self.wino_fused[cs.name] = (ff, fd)
-            uf = self._f32((40 if ff else 36) * cs.cout * cs.cp)
-            ud = self._f32((40 if fd else 36) * cs.cout * cs.cp) if cs.need_dgrad else None
-            # fused weight gradient (wino_wgrad.hip): transforms x and dy itself, so
-            # the forward keeps no V and no D is formed
-            qf = (K.wino_wgrad_fused_q(B, cs.h, cs.w, cs.cp, cs.cout)
-                  if q > 0 and wgf and min(cs.h, cs.w) >= wgf_minhw else 0)
-            v = self._f32(vc) if q > 0 and not qf else None  # None: the forward's V goes to scratch
-            self.wino_layers[cs.name] = (uf, ud, v)
-            if q > 0:
-                self.wino_wgrad.add(cs.name)
-                if qf:
-                    self.wino_wgf.add(cs.name)
-                    s_part = max(s_part, 36 * qf * cs.cout * cs.cp)
-                else:
-                    s_d = max(s_d, vk)
-                    s_part = max(s_part, 36 * q * cs.cout * cs.cp)
-                    # one pass over dz forms both backward operands (wino.hip wino_dz_xf_kernel): D
-                    # for the weight gradient and V' for the data gradient, instead of a dy
-                    # transform and an input transform that each read dy. Only with both
-                    # gradients on the compute stream: on the side stream D would be written into
-                    # scratch that stream still reads.
-                    if (self.wg_stream is None and cs.need_dgrad and not fd
-                            and K.wino_dz_ok(B, cs.h, cs.w, cs.cout)):
-                        self.wino_dz.add(cs.name)
-        # BN folded into the next conv's input transform (PSX_TUNE wino_bnfold=1, default): a block's inner
-        # BN (+ ReLU) whose only consumer is a Winograd conv with a Winograd weight gradient (that
-        # reads V, not the activation) is finalized and applied inside wino_in_kernel, so its
-        # activation is never written; the data gradient's ReLU mask comes from the BN affine
-        # (needs the masked dz store, so the BN-backward apply never reads the activation either)
-        self.wino_bnfold = {}
-        if self._fold and self.mask_store and tune_flag("wino_bnfold", True):
-            for b in self.spec.blocks:
-                for i in range(len(b.convs) - 1):
-                    nxt = b.convs[i + 1]
-                    if nxt.name in self.wino_wgrad and nxt.cin == b.bns[i].c:
-                        self.wino_bnfold[b.bns[i].name] = nxt.name
-        # main-stream scratch (forward V of layers without a Winograd weight gradient / GEMM output;
-        # data-gradient input tiles + GEMM output) and the weight-gradient side stream's own (dy
-        # tiles, GEMM partials)
-        self.wino_s1 = self._f32(max(1, s_main))
-        self.wino_s2 = self._f32(max(1, s_main))
-        self.wino_wd = self._f32(max(1, s_d))
-        self.wino_wpart = self._f32(max(1, s_part))
-        # the first block's first conv's weight gradient runs on the compute stream, concurrently
-        # with the side stream's (_bwd_stem): its own scratch
-        self.tail_split = (self.wg_stream is not None
-                           and bool(self.spec.blocks) and self.spec.blocks[0].convs[0].name in self.wino_wgrad)
-        self.wino_wd2 = self._f32(max(1, s_d)) if self.tail_split else None
-        self.wino_wpart2 = self._f32(max(1, s_part)) if self.tail_split else None
-
     def _wino_unpack(self, arena):
         """Every Winograd layer's forward and data-gradient weight transforms: the first stage's
         layers in one launch on the compute stream, the rest (ResNet-18: 9.3 M of the 9.4 M
@@ -515,22 +228,17 @@ class HipResNetEngine:
         stream, overlapped with the forward of the first stage; the compute stream waits for it
         before the first conv that reads one of them (``_wino_late_wait``)."""
         key = arena.data_ptr()
-        if getattr(self, "_wino_wb_key", None) != key:
-            convs = [cs for cs in all_convs(self.spec) if cs.name in self.wino_layers]
-            hw0 = max((cs.h for cs in convs), default=0)
-            split = self.wt_stream is not None
+        if self._wino_wb_key != key:
             early, late = [], []
-            self._wino_late = set()
-            for cs in convs:
-                u = self.wino_layers[cs.name]
+            for cs in all_convs(self.spec):
+                if cs.name not in self.wu:
+                    continue
+                p, (uf, ud, _) = self.plan.convs[cs.name], self.wu[cs.name]
                 w = self._aview(arena, f"{cs.name}.weight")
-                ff, fd = self.wino_fused[cs.name]
-                dst = early if (not split or cs.h == hw0) else late
-                if dst is late:
-                    self._wino_late.add(cs.name)
-                dst.append((w, u[0], cs.cout, cs.cp, False, int(ff)))
-                if u[1] is not None:
-                    dst.append((w, u[1], cs.cout, cs.cp, True, int(fd)))
+                dst = late if p.late else early
+                dst.append((w, uf, cs.cout, cs.cp, False, int(p.fwd == "wino_fused")))
+                if ud is not None:
+                    dst.append((w, ud, cs.cout, cs.cp, True, int(p.dgrad == "wino_fused")))
             self._wino_wb = K.WinoWeightBatch(early) if early else None
             self._wino_wb_late = K.WinoWeightBatch(late) if late else None
             self._wino_wb_key = key
@@ -540,19 +248,16 @@ class HipResNetEngine:
         if self._wino_wb_late is not None:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.dev))
-            self.wt_stream.wait_event(ev)
-            with torch.cuda.stream(self.wt_stream):
+            self.wg_stream.wait_event(ev)
+            with torch.cuda.stream(self.wg_stream):
                 self._wino_wb_late()
                 self._late_ev = torch.cuda.Event()
-                self._late_ev.record(self.wt_stream)
+                self._late_ev.record(self.wg_stream)
 
-    _late_ev = None
-    _wino_late = frozenset()
-
-    def _wino_late_wait(self, name):
+    def _wino_late_wait(self, p):
         """The compute stream waits (once per step) for the side-stream weight transforms before
         the first conv that reads one of them."""
-        if self._late_ev is not None and name in self._wino_late:
+        if self._late_ev is not None and p.late:
             torch.cuda.current_stream(self.dev).wait_event(self._late_ev)
             self._late_ev = None
 
@@ -563,102 +268,88 @@ class HipResNetEngine:
     def _aview(self, arena, name):
         return self.layout.view(arena, name)
 
+    def _bn_views(self, arena, bs: BNSpec, n=4):
+        """The first n of a BN's arena tensors: weight, bias, running_mean, running_var."""
+        return [self._aview(arena, f"{bs.name}.{k}") for k in _BN_PARAMS[:n]]
+
     def _red(self, bs: BNSpec, which: str):
-        off, n = self.bn[bs.name][which]
-        return self.red[off:off + n]
+        bp = self.plan.bns[bs.name]
+        off, rows = (bp.fwd_off, 2) if which == "fwd" else (bp.bwd_off, 3)
+        return self.red[off:off + self.plan.slot_words * rows * bs.c]
 
     def _ctr(self, bs: BNSpec, which: int) -> int:
-        return self.red.data_ptr() + 4 * (self.bn[bs.name]["ctr"] + which)
+        return self.red.data_ptr() + 4 * (self.plan.bns[bs.name].ctr + which)
 
     def _fin_fwd(self, bs: BNSpec, arena, count):
+        """The in-launch forward finalize descriptor of bs (cached per arena and count)."""
         key = ("f", bs.name, arena.data_ptr(), count)
-        f = self._fins.get(key)
-        if f is None:
+        if key not in self._fins:
             st = self.bn[bs.name]
-            f = K.bn_fin(self._aview(arena, f"{bs.name}.weight"), self._aview(arena, f"{bs.name}.bias"),
-                         self._aview(arena, f"{bs.name}.running_mean"), self._aview(arena, f"{bs.name}.running_var"),
-                         st["affine"], st["saved"], self._ctr(bs, 0), count, self.eps, self.mom, bs.c,
-                         sshift=st["sshift"], sshift_next=st["sshift_next"])
-            self._fins[key] = f
-        return f
+            self._fins[key] = K.bn_fin(*self._bn_views(arena, bs), st["affine"], st["saved"], self._ctr(bs, 0), count,
+                                       self.eps, self.mom, bs.c, sshift=st["sshift"], sshift_next=st["sshift_next"])
+        return self._fins[key]
 
     def _fin_bwd(self, bs: BNSpec, arena, count):
         key = ("b", bs.name, arena.data_ptr(), count)
-        f = self._fins.get(key)
-        if f is None:
+        if key not in self._fins:
             st = self.bn[bs.name]
-            f = K.bn_bwd_fin(self._aview(arena, f"{bs.name}.weight"), st["saved"], st["coef"],
-                             self._gptr(f"{bs.name}.weight"), self._gptr(f"{bs.name}.bias"), self._ctr(bs, 1), count,
-                             1.0, bs.c, self.grad_fp16)
-            self._fins[key] = f
-        return f
+            self._fins[key] = K.bn_bwd_fin(self._aview(arena, f"{bs.name}.weight"), st["saved"], st["coef"],
+                                           self._gptr(f"{bs.name}.weight"), self._gptr(f"{bs.name}.bias"),
+                                           self._ctr(bs, 1), count, 1.0, bs.c, self.grad_fp16)
+        return self._fins[key]
 
     def _conv_bn_fwd(self, cs: ConvSpec, x, y, bs: BNSpec, arena, train: bool, bn_in=None):
         """conv -> (train) batch statistics + BN finalize | (eval) running-statistics affine.
-        With conv v2 the finalize runs inside the conv launch (last workgroup, bnfin.hpp)."""
+        With conv v2 the finalize can run inside the conv launch (last workgroup, bnfin.hpp)."""
+        p, fin_at = self.plan.convs[cs.name], self.plan.bns[bs.name].fwd_fin
         oh, ow = cs.out_hw
         npix = self.B * oh * ow
-        wf = self.wbuf[cs.wf_off:cs.wf_off + cs.cout * cs.kg]
         stats = self._red(bs, "fwd") if train else None
-        fin = self._fin_fwd(bs, arena, npix) if (train and self.fuse_fin) else None
-        wl = self.wino_layers.get(cs.name)
-        assert bn_in is None or wl is not None, cs.name
         sshift = self.bn[bs.name]["sshift"] if train else None
-        if wl is not None:
-            self._wino_late_wait(cs.name)
-            if self.wino_fused[cs.name][0]:
-                K.wino_fused(x, wl[0], y, None, stats, wl[2], self.B, cs.h, cs.w, cs.cp, cs.cout, bn_in=bn_in,
-                             sshift=sshift)
+        assert bn_in is None or p.wino, cs.name
+        if p.wino:
+            uf, _, v = self.wu[cs.name]
+            self._wino_late_wait(p)
+            if p.fwd == "wino_fused":
+                K.wino_fused(x, uf, y, None, stats, v, self.B, cs.h, cs.w, cs.cp, cs.cout, bn_in=bn_in, sshift=sshift)
             else:
-                v = wl[2] if wl[2] is not None else self.wino_s2
-                K.wino_conv(x, wl[0], y, None, stats, v, self.wino_s1, self.B, cs.h, cs.w, cs.cp, cs.cout,
-                            bn_in=bn_in, sshift=sshift)
-            if not train:
-                self._bn_eval(bs, arena)
-            elif not self._fold:  # no in-launch finalize on this path
-                self._bn_train(bs, arena, self.nslots, npix)
-            return
-        if not (self.stem_direct and fin is None and cs.cin == 3 and (cs.k, cs.stride, cs.pad) in ((3, 1, 1), (7, 2, 3))
-                and K.stem_conv(x, wf, y, stats, self.B, cs.h, cs.w, cs.cin, cs.cp, cs.cout, cs.kg, sshift=sshift,
-                                k=cs.k)):
-            K.conv_fwd2(x, wf, y, stats, self.wpart, self.B, cs.h, cs.w, cs.cp, cs.cout, cs.k, cs.stride, cs.pad,
-                        cs.kg, fin=fin, sshift=sshift)
+                K.wino_conv(x, uf, y, None, stats, v if v is not None else self.wino_s2, self.wino_s1, self.B, cs.h,
+                            cs.w, cs.cp, cs.cout, bn_in=bn_in, sshift=sshift)
+        else:
+            wf = self.wbuf[p.wf_off:p.wf_off + cs.cout * cs.kg]
+            if p.fwd == "stem":
+                if not K.stem_conv(x, wf, y, stats, self.B, cs.h, cs.w, cs.cin, cs.cp, cs.cout, cs.kg, sshift=sshift,
+                                   k=cs.k):
+                    raise RuntimeError(f"{cs.name}: the planned direct stem kernel refused the shape")
+            else:
+                fin = self._fin_fwd(bs, arena, npix) if (train and fin_at == "conv") else None
+                K.conv_fwd2(x, wf, y, stats, self.wpart, self.B, cs.h, cs.w, cs.cp, cs.cout, cs.k, cs.stride, cs.pad,
+                            cs.kg, fin=fin, sshift=sshift)
         if not train:
             self._bn_eval(bs, arena)
-        elif fin is None and not self._fold:
+        elif fin_at == "separate":
             self._bn_train(bs, arena, self.nslots, npix)
 
-    @property
-    def _fold(self) -> bool:
-        return self.fin_apply and not self.fuse_fin
-
     def _apply(self, bs: BNSpec, y, out, arena, train: bool, res=None, bs2: BNSpec | None = None):
-        """BN (+ residual, + shortcut BN bs2 on res) + ReLU; with fin_apply the training-mode
-        finalize of bs (and bs2) runs inside this launch."""
+        """BN (+ residual, + shortcut BN bs2 on res) + ReLU; with bn_finalize "apply" the
+        training-mode finalize of bs (and bs2) runs inside this launch."""
         c = bs.c
-        if train and self._fold:
+        if train and self.plan.bns[bs.name].fwd_fin == "apply":
             npix = y.numel() // c
-            if bs2 is not None:
-                K.bn_apply_fin(y, self._red(bs, "fwd"), self._fin_fwd(bs, arena, npix), out, c, relu=True, res=res,
-                               part2=self._red(bs2, "fwd"), fin2=self._fin_fwd(bs2, arena, npix))
-            else:
-                K.bn_apply_fin(y, self._red(bs, "fwd"), self._fin_fwd(bs, arena, npix), out, c, relu=True, res=res)
+            two = dict(part2=self._red(bs2, "fwd"), fin2=self._fin_fwd(bs2, arena, npix)) if bs2 is not None else {}
+            K.bn_apply_fin(y, self._red(bs, "fwd"), self._fin_fwd(bs, arena, npix), out, c, relu=True, res=res, **two)
             return
         K.bn_apply(y, self.bn[bs.name]["affine"], out, c, relu=True, res=res,
                    affine2=self.bn[bs2.name]["affine"] if bs2 is not None else None)
 
     def _bn_train(self, bs: BNSpec, arena, T, count):
         st = self.bn[bs.name]
-        K.bn_finalize(self._red(bs, "fwd"), T, bs.c, count, self._aview(arena, f"{bs.name}.weight"),
-                      self._aview(arena, f"{bs.name}.bias"), self.eps, self.mom,
-                      self._aview(arena, f"{bs.name}.running_mean"), self._aview(arena, f"{bs.name}.running_var"),
-                      st["affine"], st["saved"], sshift=st["sshift"], sshift_next=st["sshift_next"])
+        w, b, rm, rv = self._bn_views(arena, bs)
+        K.bn_finalize(self._red(bs, "fwd"), T, bs.c, count, w, b, self.eps, self.mom, rm, rv, st["affine"],
+                      st["saved"], sshift=st["sshift"], sshift_next=st["sshift_next"])
 
     def _bn_eval(self, bs: BNSpec, arena):
-        st = self.bn[bs.name]
-        K.bn_eval_affine(bs.c, self._aview(arena, f"{bs.name}.weight"), self._aview(arena, f"{bs.name}.bias"),
-                         self._aview(arena, f"{bs.name}.running_mean"), self._aview(arena, f"{bs.name}.running_var"),
-                         self.eps, st["affine"])
+        K.bn_eval_affine(bs.c, *self._bn_views(arena, bs), self.eps, self.bn[bs.name]["affine"])
 
     def _side(self):
         """Weight gradients only feed the push, so they run on a side stream concurrently with
@@ -675,28 +366,7 @@ class HipResNetEngine:
         if self.wg_stream is not None:
             torch.cuda.current_stream(self.dev).wait_stream(self.wg_stream)
 
-    def _plan_wpart(self, max_wp: int) -> int:
-        """Batched weight-gradient reduction (PSX_TUNE wgrad_rbatch, default on): the layers of one
-        residual block keep their split-K partials in disjoint slices of wpart_w until ONE
-        wgrad_reduce_batch launch at the end of the block's backward reduces them all (8 launches
-        instead of 19 for ResNet-18). Returns the fp32 size wpart_w needs."""
-        self.rbatch = tune_flag("wgrad_rbatch", True)
-        if not self.rbatch:
-            return max_wp
-        need = max_wp
-        for b in self.spec.blocks:
-            convs = list(b.convs) + ([b.down[0]] if b.down else [])
-            if len(convs) > K.WRBATCH_MAX:
-                continue
-            off = 0
-            for cs in convs:
-                cs.wp_off = off
-                off += cs.wp
-            need = max(need, off)
-        return need
-
-    def _wgrad(self, cs: ConvSpec, x, dy):
-        fold = self._bwd_fold.get(cs.name)
+    def _wgrad(self, cs: ConvSpec, x, dy, fold=None):
         if self._wg_batch is not None:  # deferred: issued together at the end of the unit
             self._wg_batch.append((cs, x, dy, fold))
             return
@@ -711,39 +381,35 @@ class HipResNetEngine:
                     self._wgrad_now(cs, x, dy, fold)
 
     def _wgrad_now(self, cs: ConvSpec, x, dy, fold=None, scratch=None):
-        if cs.name in self.wino_wgf:  # fused Winograd weight gradient straight into the wire
-            wpart = scratch[1] if scratch is not None else self.wino_wpart
-            xf = self._xfold.get(cs.name)  # its input was never written: y + the BN affine instead
-            K.wino_wgrad_fused(xf[0] if xf else x, dy, wpart, self.layout.grad_view(self.grads, f"{cs.name}.weight"),
-                               self.B, cs.h, cs.w, cs.cp, cs.cout, xaff=xf[1] if xf else None, bwd_in=fold)
+        """cs's weight gradient by its planned route. fold: the BN-backward apply in front of it is
+        folded into its dy load (_grad_operands); scratch = (dy tiles, partials) of the tail one."""
+        p = self.plan.convs[cs.name]
+        wd, wpart = scratch if scratch is not None else (self.wino_wd, self.wino_wpart) if p.wino else (None, None)
+        if p.wgrad == "wgrad2":
+            assert fold is None, cs.name
+            part = self.wpart_w[p.wp_off:p.wp_off + p.wp]
+            K.conv_wgrad2(x, dy, part, self.B, cs.h, cs.w, cs.cp, cs.cout, cs.k, cs.stride, cs.pad, cs.kg)
+            item = (part, p.splits, cs.cout, cs.kg, cs.cin, cs.cp, cs.k, self._gptr(f"{cs.name}.weight"))
+            if p.rbatch:
+                self._wr_batch.append(item)  # reduced with the block's other layers (_flush_reduces)
+            else:
+                K.wgrad_reduce(*item[:7], 1.0, item[7], self.grad_fp16)
             return
-        if cs.name in self.wino_dz and scratch is None:
+        out = self.layout.grad_view(self.grads, f"{cs.name}.weight")  # straight into the wire: nothing to reduce
+        if p.wgrad == "wino_fused":
+            xf = self.xsrc.get(cs.name)  # its input was never written: y + the BN affine instead
+            K.wino_wgrad_fused(xf[0] if xf else x, dy, wpart, out, self.B, cs.h, cs.w, cs.cp, cs.cout,
+                               xaff=xf[1] if xf else None, bwd_in=fold)
+        elif p.wgrad == "wino_dz":
             # both operands from one pass over dy (with ``fold``: over dz, the BN apply folded in
             # and its coefficients published): D here, V' left in wino_s1 for _dgrad, which
             # follows; nothing of the weight-gradient chain touches wino_s1
             # rounded as the apply pass (as_apply): the step equals the unfolded one bit for bit
-            K.check(K.wino_dz_xf(dy, self.wino_s1, self.wino_wd, self.B, cs.h, cs.w, cs.cout, bwd_in=fold,
-                                 as_apply=True), "wino_dz_xf")
-            self._dz_pre = cs.name
-            K.wino_wgrad_pre(self.wino_layers[cs.name][2], self.wino_wd, self.wino_wpart,
-                             self.layout.grad_view(self.grads, f"{cs.name}.weight"), self.B, cs.h, cs.w, cs.cp, cs.cout)
-            return
-        if cs.name in self.wino_wgrad:  # straight into the wire: no split partials to reduce
-            wd, wpart = scratch if scratch is not None else (self.wino_wd, self.wino_wpart)
-            K.wino_wgrad(self.wino_layers[cs.name][2], dy, wd, wpart,
-                         self.layout.grad_view(self.grads, f"{cs.name}.weight"), self.B, cs.h, cs.w, cs.cp, cs.cout,
-                         bwd_in=fold)
-            return
-        assert fold is None, cs.name
-        part = self.wpart_w[cs.wp_off:cs.wp_off + cs.wp]
-        K.conv_wgrad2(x, dy, part, self.B, cs.h, cs.w, cs.cp, cs.cout, cs.k, cs.stride, cs.pad, cs.kg)
-        item = (part, cs.splits, cs.cout, cs.kg, cs.cin, cs.cp, cs.k, self._gptr(f"{cs.name}.weight"))
-        if self._wr_batch is not None and K.wgrad_reduce_batchable(cs.cp, cs.k):
-            self._wr_batch.append(item)  # reduced with the block's other layers (_flush_reduces)
-            return
-        K.wgrad_reduce(*item[:7], 1.0, item[7], self.grad_fp16)
-
-    _wr_batch = None
+            K.check(K.wino_dz_xf(dy, self.wino_s1, wd, self.B, cs.h, cs.w, cs.cout, bwd_in=fold, as_apply=True),
+                    "wino_dz_xf")
+            K.wino_wgrad_pre(self.wu[cs.name][2], wd, wpart, out, self.B, cs.h, cs.w, cs.cp, cs.cout)
+        else:
+            K.wino_wgrad(self.wu[cs.name][2], dy, wd, wpart, out, self.B, cs.h, cs.w, cs.cp, cs.cout, bwd_in=fold)
 
     def _flush_reduces(self):
         batch, self._wr_batch = self._wr_batch, None
@@ -751,136 +417,76 @@ class HipResNetEngine:
             with self._side():
                 K.wgrad_reduce_batch(batch, 1.0, self.grad_fp16)
 
-    def _dgrad(self, cs: ConvSpec, dy, dx, res=None, bn_next=None, sc=None):
-        """bn_next = (BNSpec, o, y, two|None): the BN whose backward consumes dx; with conv v2 its
-        reduction (sum dz, sum dz*xhat) is produced by the dgrad epilogue (fuse_bnbwd).
-        sc = (shortcut ConvSpec, its output gradient): fold the block's 1x1 / stride-2 shortcut
-        data gradient into this 3x3 / stride-2 launch; returns False (nothing launched) when the
-        layer cannot fold."""
-        wl = self.wino_layers.get(cs.name)
-        if sc is not None:
-            ds, dys_sc = sc
-            if wl is not None or cs.k != 3 or cs.stride != 2 or cs.pad != 1 or ds.k != 1 or ds.stride != 2 \
-                    or ds.pad != 0 or ds.cp != cs.cp or ds.cout != cs.cout or ds.kgd != cs.cout:
-                return False
+    def _dgrad(self, cs: ConvSpec, dy, dx, res=None, bn_next=None, sc=None, fold=None):
+        """cs's data gradient by its planned route. bn_next = (BNSpec, o, y, two|None): the BN whose
+        backward consumes dx; where the plan says so its reduction (sum dz, sum dz*xhat) is
+        produced by this launch's epilogue. sc = (shortcut ConvSpec, its output gradient) on the
+        "conv2_sc" route: the block's 1x1 / stride-2 shortcut data gradient folded into this
+        3x3 / stride-2 launch. fold: as for _wgrad_now."""
+        p = self.plan.convs[cs.name]
         bst = None
-        if bn_next is not None and self.fuse_bnbwd:
+        if bn_next is not None and self.plan.bns[bn_next[0].name].bwd_sums == "dgrad":
             bs, o, y, two = bn_next
-            st = self.bn[bs.name]
-            ms = self.mask_store
-            if bs.name in self.wino_bnfold:  # o was never written: the mask comes from the affine
+            st, ms = self.bn[bs.name], self.plan.bns[bs.name].premasked
+            if bs.name in self.plan.bnfold:  # o was never written: the mask comes from the affine
                 bst = K.bwd_stats_desc(self._red(bs, "bwd"), None, y, st["saved"], mask_store=ms,
                                        mask_aff=st["affine"])
-            elif two is None:
-                bst = K.bwd_stats_desc(self._red(bs, "bwd"), o, y, st["saved"], mask_store=ms)
             else:
-                bs2, y2 = two
-                bst = K.bwd_stats_desc(self._red(bs, "bwd"), o, y, st["saved"], y2, self.bn[bs2.name]["saved"],
-                                       mask_store=ms)
-            self._prereduced.add(bs.name)
-            if ms:
-                self._premasked.add(bs.name)
-        if wl is not None:  # Winograd: the output transform produces the same fused sums
-            if self.wino_fused[cs.name][1]:
-                K.wino_fused(dy, wl[1], dx, res, None, None, self.B, cs.h, cs.w, cs.cout, cs.cp, bst=bst,
-                             bwd_in=self._bwd_fold.get(cs.name))
-            elif self._dz_pre == cs.name:  # its transformed input is in wino_s1 already (_wgrad_now)
-                self._dz_pre = None
-                K.wino_conv_pre(self.wino_s1, wl[1], dx, res, None, self.wino_s2, self.B, cs.h, cs.w, cs.cout,
-                                cs.cp, bst=bst)
+                y2, saved2 = (two[1], self.bn[two[0].name]["saved"]) if two is not None else (None, None)
+                bst = K.bwd_stats_desc(self._red(bs, "bwd"), o, y, st["saved"], y2, saved2, mask_store=ms)
+        geo = (self.B, cs.h, cs.w, cs.cout, cs.cp)
+        if p.wino:  # Winograd: the output transform produces the same fused sums
+            ud = self.wu[cs.name][1]
+            if p.dgrad == "wino_fused":
+                K.wino_fused(dy, ud, dx, res, None, None, *geo, bst=bst, bwd_in=fold)
+            elif p.dgrad == "wino_pre":  # its transformed input is in wino_s1 already (_wgrad_now)
+                K.wino_conv_pre(self.wino_s1, ud, dx, res, None, self.wino_s2, *geo, bst=bst)
             else:
-                assert cs.name not in self._bwd_fold, cs.name  # a folded dy exists in no buffer
-                K.wino_conv(dy, wl[1], dx, res, None, self.wino_s1, self.wino_s2, self.B, cs.h, cs.w, cs.cout,
-                            cs.cp, bst=bst)
+                assert fold is None, cs.name  # a folded dy exists in no buffer
+                K.wino_conv(dy, ud, dx, res, None, self.wino_s1, self.wino_s2, *geo, bst=bst)
             return
-        wd = self.wbuf[cs.wd_off:cs.wd_off + cs.cp * cs.kgd]
-        if sc is not None:
-            wds = self.wbuf[ds.wd_off:ds.wd_off + ds.cp * ds.kgd]
-            if not K.conv_dgrad2_sc(dy, wd, dx, self.wpart, self.B, cs.h, cs.w, cs.cp, cs.cout, cs.kgd, dys_sc, wds,
-                                    ds.kgd, bst=bst):
-                if bn_next is not None and self.fuse_bnbwd:  # nothing ran: the sums are not produced
-                    self._prereduced.discard(bn_next[0].name)
-                    self._premasked.discard(bn_next[0].name)
-                return False
-            return True
+        wd = self.wbuf[p.wd_off:p.wd_off + cs.cp * cs.kgd]
+        if p.dgrad == "conv2_sc":
+            ds, dys_sc = sc
+            pd = self.plan.convs[ds.name]
+            if not K.conv_dgrad2_sc(dy, wd, dx, self.wpart, self.B, cs.h, cs.w, cs.cp, cs.cout, cs.kgd, dys_sc,
+                                    self.wbuf[pd.wd_off:pd.wd_off + ds.cp * ds.kgd], ds.kgd, bst=bst):
+                raise RuntimeError(f"{cs.name}: the planned shortcut fold was refused")
+            return
         K.conv_dgrad2(dy, wd, dx, res, self.wpart, self.B, cs.h, cs.w, cs.cp, cs.cout, cs.k, cs.stride, cs.pad,
                       cs.kgd, bst=bst)
-
-    def _bn_bwd_to(self, cs: ConvSpec, bs: BNSpec, arena, g, o, y, dx, npix, dzout=None):
-        """The backward of BN bs whose output gradient feeds only conv cs's data and weight
-        gradients. Returns (dz, dy): dz as _bn_bwd returns it, dy the buffer cs's gradients read.
-        Folded (PSX_TUNE wino_bwdfold=1, default: cs has the fused Winograd data gradient and a Winograd
-        weight gradient, g is already the masked dz and its sums came from the producing dgrad's
-        epilogue): no apply pass — dy = k1 dz + k2 y + k3 is formed inside both consumers'
-        operand loads (wino_fused.hip, wino.hip dy transform), and the fused data gradient
-        publishes the coefficients and dgamma / dbeta. A three-launch layer in ``wino_dz`` folds
-        too: its one pass over dz (wino.hip wino_dz_xf_kernel) is both consumers' load and the
-        publisher, and rounds dy as the apply pass would (bit-equal to the unfolded step)."""
-        ok = (self.bwd_fold and self._fold and bs.name in self._premasked and bs.name in self._prereduced
-              and cs.name in self.wino_wgrad
-              and (self.wino_fused.get(cs.name, (False, False))[1] or cs.name in self.wino_dz))
-        if not ok:
-            dz = self._bn_bwd(bs, arena, g, o, y, dx, npix, dzout=dzout)
-            return dz, dx
-        self._premasked.discard(bs.name)
-        self._prereduced.discard(bs.name)
-        self._bwd_fold[cs.name] = (y, self._red(bs, "bwd"), self._fin_bwd(bs, arena, npix))
-        return g, g
 
     def _bn_bwd(self, bs: BNSpec, arena, g, o, y, dx, npix, two=None, dzout=None):
         """BN (+ReLU mask from o) backward; two = (bs2, y2, dx2) for a shared-dz second BN.
         Returns the buffer that holds dz = g*[o > 0]: ``g`` itself when the producing dgrad stored
-        it masked (mask_store), else ``dzout`` (written here when given)."""
-        if bs.name in self._premasked:
-            self._premasked.discard(bs.name)
-            self._bn_bwd_body(bs, arena, g, None, y, dx, npix, two, None)
-            return g
-        self._bn_bwd_body(bs, arena, g, o, y, dx, npix, two, dzout)
-        return dzout
+        it masked, else ``dzout`` (written here when given)."""
+        bp, st, part = self.plan.bns[bs.name], self.bn[bs.name], self._red(bs, "bwd")
+        if bp.premasked:
+            o = dzout = None
+        pre = bp.bwd_sums != "reduce"  # sums already produced by a dgrad epilogue or the head
+        bs2, y2, dx2 = two if two is not None else (None, None, None)
+        st2 = self.bn[bs2.name] if bs2 is not None else None
 
-    def _bn_bwd_body(self, bs: BNSpec, arena, g, o, y, dx, npix, two, dzout):
-        st = self.bn[bs.name]
-        part = self._red(bs, "bwd")
-        fuse = self.fuse_fin
-        pre = bs.name in self._prereduced  # sums already produced by the dgrad epilogue
-        self._prereduced.discard(bs.name)
-        if pre:
-            fuse = False
-        if self._fold and not fuse:  # finalize inside the apply launch
-            if two is None:
-                if not pre:
-                    K.bn_bwd_reduce(g, o, y, st["saved"], part, npix, bs.c)
-                K.bn_bwd_apply_fin(g, o, y, part, self._fin_bwd(bs, arena, npix), dx, bs.c, dzout=dzout)
-            else:
-                bs2, y2, dx2 = two
-                if not pre:
-                    K.bn_bwd_reduce(g, o, y, st["saved"], part, npix, bs.c, y2=y2, saved2=self.bn[bs2.name]["saved"])
-                K.bn_bwd_apply_fin(g, o, y, part, self._fin_bwd(bs, arena, npix), dx, bs.c, y2=y2,
-                                   fin2=self._fin_bwd(bs2, arena, npix), dx2=dx2, dzout=dzout)
-            return
-        if two is None:
-            T = self.nslots if pre else K.bn_bwd_reduce(g, o, y, st["saved"], part, npix, bs.c,
-                                                        fin1=self._fin_bwd(bs, arena, npix) if fuse else None)
-            if not fuse:
-                K.bn_bwd_finalize(part, T, 2, 1, bs.c, npix, self._aview(arena, f"{bs.name}.weight"),
-                                  st["saved"], st["coef"], self._gptr(f"{bs.name}.weight"),
-                                  self._gptr(f"{bs.name}.bias"), 1.0, self.grad_fp16)
-            K.bn_bwd_apply(g, o, y, st["coef"], dx, bs.c, dzout=dzout)
-        else:
-            bs2, y2, dx2 = two
-            st2 = self.bn[bs2.name]
-            T = self.nslots if pre else K.bn_bwd_reduce(g, o, y, st["saved"], part, npix, bs.c, y2=y2,
-                                                        saved2=st2["saved"],
-                                                        fin1=self._fin_bwd(bs, arena, npix) if fuse else None,
-                                                        fin2=self._fin_bwd(bs2, arena, npix) if fuse else None)
-            if not fuse:
-                K.bn_bwd_finalize(part, T, 3, 1, bs.c, npix, self._aview(arena, f"{bs.name}.weight"),
-                                  st["saved"], st["coef"], self._gptr(f"{bs.name}.weight"),
-                                  self._gptr(f"{bs.name}.bias"), 1.0, self.grad_fp16)
-                K.bn_bwd_finalize(part, T, 3, 2, bs2.c, npix, self._aview(arena, f"{bs2.name}.weight"),
-                                  st2["saved"], st2["coef"], self._gptr(f"{bs2.name}.weight"),
-                                  self._gptr(f"{bs2.name}.bias"), 1.0, self.grad_fp16)
-            K.bn_bwd_apply(g, o, y, st["coef"], dx, bs.c, y2=y2, coef2=st2["coef"], dx2=dx2, dzout=dzout)
+        def fin(b, on=True):
+            return self._fin_bwd(b, arena, npix) if on and b is not None else None
+
+        if self.opts.bn_finalize == "apply":  # finalize inside the apply launch
+            if not pre:
+                K.bn_bwd_reduce(g, o, y, st["saved"], part, npix, bs.c, y2=y2, saved2=st2 and st2["saved"])
+            K.bn_bwd_apply_fin(g, o, y, part, fin(bs), dx, bs.c, y2=y2, fin2=fin(bs2), dx2=dx2, dzout=dzout)
+            return g if bp.premasked else dzout
+        fuse = self.opts.bn_finalize == "conv" and not pre  # finalize in the reduce launch's last block
+        T = self.nslots if pre else K.bn_bwd_reduce(g, o, y, st["saved"], part, npix, bs.c, y2=y2,
+                                                    saved2=st2 and st2["saved"], fin1=fin(bs, fuse),
+                                                    fin2=fin(bs2, fuse))
+        if not fuse:
+            for which, (b_, s_) in enumerate([(bs, st)] + ([(bs2, st2)] if bs2 is not None else []), 1):
+                K.bn_bwd_finalize(part, T, 2 if bs2 is None else 3, which, b_.c, npix,
+                                  self._aview(arena, f"{b_.name}.weight"), s_["saved"], s_["coef"],
+                                  self._gptr(f"{b_.name}.weight"), self._gptr(f"{b_.name}.bias"), 1.0, self.grad_fp16)
+        K.bn_bwd_apply(g, o, y, st["coef"], dx, bs.c, y2=y2, coef2=st2 and st2["coef"], dx2=dx2, dzout=dzout)
+        return g if bp.premasked else dzout
+
 
     # ------------------------------------------------------------------ public API
     def unpack(self, arena: torch.Tensor):
@@ -889,12 +495,8 @@ class HipResNetEngine:
         WeightWire: the server's apply wrote those bits; identical operands either way)."""
         src = self.wsrc if self.wsrc is not None else arena
         K.param_unpack_tiles(src, self.descs, self.ndesc, self.ntiles, self.wbuf, scatter=self.small_scatter)
-        if self.wino_layers:
+        if self.wu:
             self._wino_unpack(arena)
-
-    small_scatter = None
-    _zeroed = False       # red zeroed by this step's augment launch (consumed by forward)
-    _zeroed_head = False  # correct zeroed by it (consumed by head)
 
     def set_weight_source(self, img: torch.Tensor | None, pre_unpack=None, scatter=None):
         """Read conv weights from a bf16 image (same offsets as the arena's parameter prefix)
@@ -947,10 +549,9 @@ class HipResNetEngine:
                 bn_in = None
                 if i < L - 1:
                     bs = b.bns[i]
-                    if train and bs.name in self.wino_bnfold:  # applied by the next conv's input transform
+                    if train and self.plan.bns[bs.name].fwd_fin == "next_conv":  # applied by its input transform
                         bn_in = (self._red(bs, "fwd"), self._fin_fwd(bs, arena, d["y"][i].numel() // bs.c))
                         src = d["y"][i]
-                        self._xfold[b.convs[i + 1].name] = (d["y"][i], self.bn[bs.name]["affine"])
                         continue
                     self._apply(bs, d["y"][i], d["a"][i], arena, train)
                     src = d["a"][i]
@@ -970,19 +571,18 @@ class HipResNetEngine:
         # the last block's output BN: its backward sums come out of the head launch (one
         # bn_bwd_reduce pass fewer) when the fused per-sample head runs and that BN has no
         # shortcut BN sharing its gradient
-        bst, last = None, None
-        if backward and self.fuse_bnbwd and sp.blocks and not sp.blocks[-1].down:
+        bst = None
+        if backward and sp.blocks and self.plan.bns[sp.blocks[-1].bns[-1].name].bwd_sums == "head":
             last = sp.blocks[-1].bns[-1]
             bst = K.bwd_stats_desc(self._red(last, "bwd"), self.final, self.blk[-1]["y"][-1],
                                    self.bn[last.name]["saved"])
         fused = K.head_fwd_bwd(self.final, self.B, self.head_hw, sp.fc_in, self._aview(arena, f"{sp.fc}.weight"),
                                self._aview(arena, f"{sp.fc}.bias"), sp.classes, self.labels, self.pooled,
                                self.dlogits, self.dfinal if backward else None, self.loss, self.correct, bst=bst)
-        if fused and last is not None:
-            self._prereduced.add(last.name)
+        if bst is not None and not fused:
+            raise RuntimeError("the head did not produce the planned BN-backward sums")
 
     def _bwd_fc(self, arena):
-        self._bwd_fold = {}  # the first backward unit: this step's folds are recorded afresh
         sp = self.spec
         with self._side():
             K.head_wgrad(self.dlogits, self.pooled, self.B, sp.classes, sp.fc_in, self._gptr(f"{sp.fc}.weight"),
@@ -990,72 +590,92 @@ class HipResNetEngine:
 
     def _bwd_block(self, arena, j: int):
         """Backward of residual block j; its incoming gradient is the next block's input grad.
-        With the side stream its weight gradients are issued as one batch after the block."""
+        With the side stream its weight gradients are issued as one batch after the block, and its
+        direct ones' split-K partials reduced by one launch (plan: ConvPlan.rbatch)."""
         self._wg_batch = [] if self.wg_stream is not None else None
-        b = self.spec.blocks[j]
-        nconv = len(b.convs) + (1 if b.down else 0)
-        self._wr_batch = [] if self.rbatch and nconv <= K.WRBATCH_MAX else None
+        self._wr_batch = []
         try:
             self._bwd_block_body(arena, j)
         finally:
-            if j == 0 and self._split_tail() and self._wg_batch:
-                # the step's tail: this weight gradient runs on the compute stream after the stem's
-                # BN backward (_bwd_stem), concurrently with the side stream's, instead of after it
-                first = self.spec.blocks[0].convs[0].name
-                keep = [it for it in self._wg_batch if it[0].name != first]
-                self._tail_wgrad = [it for it in self._wg_batch if it[0].name == first] or None
-                self._wg_batch = keep
             self._flush_wgrads()
             self._flush_reduces()
 
-    _tail_wgrad = None
-    tail_split = False
-    wino_wd2 = wino_wpart2 = None
-
     def _split_tail(self) -> bool:
-        """Only when block 0 and the stem end in the same backward segment (a gradient bucket is
-        pushed when its segment ends)."""
-        if not self.tail_split:
+        """The tail weight gradient (ConvPlan.tail) leaves block 0's batch for the compute stream,
+        after the stem's BN backward (_bwd_stem), concurrently with the side stream's instead of
+        after it: only when block 0 and the stem end in the same backward segment (a gradient
+        bucket is pushed when its segment ends)."""
+        if not self.plan.tail_split:
             return False
         if self.segments is None:
             return True
         key = ".".join(self.spec.blocks[0].convs[0].name.split(".")[:2])
         return any(key in g and "stem" in g for g in self.segments)
 
+    def _gin(self, j: int, i: int):
+        """The gradient wrt the output of block j's BN i (+ ReLU)."""
+        d = self.blk[j]
+        if i < len(d["da"]):
+            return d["da"][i]
+        return self.blk[j + 1]["gin"] if j + 1 < len(self.blk) else self.dfinal
+
+    def _grad_operands(self, arena, j: int, i: int):
+        """(x, dy, fold) that the gradients of block j's conv i read. Where the BN-backward apply in
+        front of it is folded (PSX_TUNE wino_bwdfold=1, default: the conv has the fused Winograd
+        data gradient and a Winograd weight gradient, the BN's incoming gradient is already the
+        masked dz and its sums came from the producing dgrad's epilogue) there is no apply pass:
+        dy = k1 dz + k2 y + k3 is formed inside both consumers' operand loads (wino_fused.hip,
+        wino.hip dy transform) from fold = (y, sums, finalize descriptor), and the fused data
+        gradient publishes the coefficients and dgamma / dbeta. A three-launch "wino_dz" layer
+        folds too: its one pass over dz (wino.hip wino_dz_xf_kernel) is both consumers' load and the
+        publisher, and rounds dy as the apply pass would (bit-equal to the unfolded step)."""
+        b, d = self.spec.blocks[j], self.blk[j]
+        x = d["inp"] if i == 0 else d["a"][i - 1]
+        if not self.plan.convs[b.convs[i].name].bwd_fold:
+            return x, d["dy"][i], None
+        g, bs = self._gin(j, i), b.bns[i]
+        return x, g, (d["y"][i], self._red(bs, "bwd"), self._fin_bwd(bs, arena, g.numel() // bs.c))
+
+    def _bn_bwd_to(self, arena, j: int, i: int, dzout=None):
+        """The backward of block j's BN i, whose output gradient feeds only conv i's gradients: a
+        pass of its own unless folded into them (_grad_operands). Returns the buffer holding dz."""
+        b, d = self.spec.blocks[j], self.blk[j]
+        g, bs = self._gin(j, i), b.bns[i]
+        if self.plan.bns[bs.name].bwd_apply == "folded":
+            return g
+        o = d["a"][i] if i < len(d["a"]) else d["out"]
+        return self._bn_bwd(bs, arena, g, o, d["y"][i], d["dy"][i], g.numel() // bs.c, dzout=dzout)
+
     def _bwd_block_body(self, arena, j: int):
-        sp, B = self.spec, self.B
-        b, d = sp.blocks[j], self.blk[j]
-        g = self.blk[j + 1]["gin"] if j + 1 < len(self.blk) else self.dfinal
+        b, d = self.spec.blocks[j], self.blk[j]
         L = len(b.convs)
-        last = b.convs[-1]
-        oh, ow = last.out_hw
-        npix = B * oh * ow
-        dys = list(d["dy"])  # the buffers each conv's gradients read (dz where a BN apply is folded)
         if b.down:
             ds, dbn = b.down
-            self._bn_bwd(b.bns[-1], arena, g, d["out"], d["y"][-1], d["dy"][-1], npix, two=(dbn, d["ys"], d["dys"]))
+            g = self._gin(j, L - 1)
+            self._bn_bwd(b.bns[-1], arena, g, d["out"], d["y"][-1], d["dy"][-1], g.numel() // dbn.c,
+                         two=(dbn, d["ys"], d["dys"]))
         else:
-            dz, dys[-1] = self._bn_bwd_to(b.convs[-1], b.bns[-1], arena, g, d["out"], d["y"][-1], d["dy"][-1], npix,
-                                          dzout=d["dz"])
+            dz = self._bn_bwd_to(arena, j, L - 1, dzout=d["dz"])
         for i in range(L - 1, -1, -1):
             cs = b.convs[i]
-            x_in = d["inp"] if i == 0 else d["a"][i - 1]
-            self._wgrad(cs, x_in, dys[i])
+            x, dy, fold = self._grad_operands(arena, j, i)
+            if not (self.plan.convs[cs.name].tail and self._split_tail()):
+                self._wgrad(cs, x, dy, fold)
             if i > 0:
-                self._dgrad(cs, dys[i], d["da"][i - 1], bn_next=(b.bns[i - 1], d["a"][i - 1], d["y"][i - 1], None))
-                _, dys[i - 1] = self._bn_bwd_to(b.convs[i - 1], b.bns[i - 1], arena, d["da"][i - 1], d["a"][i - 1],
-                                                d["y"][i - 1], d["dy"][i - 1], B * cs.h * cs.w)
+                self._dgrad(cs, dy, d["da"][i - 1], bn_next=(b.bns[i - 1], d["a"][i - 1], d["y"][i - 1], None),
+                            fold=fold)
+                self._bn_bwd_to(arena, j, i - 1)
             elif b.down:
-                ds, dbn = b.down
                 self._wgrad(ds, d["inp"], d["dys"])
                 # the 1x1 / stride-2 shortcut's data gradient folded into the 3x3 / stride-2 one
                 # (a layer the kernel cannot fold: two launches + a residual pass)
-                if not (self.fold_sc and self._dgrad(cs, dys[0], d["gin"], bn_next=self._bn_into(j),
-                                                     sc=(ds, d["dys"]))):
+                if self.plan.convs[cs.name].dgrad == "conv2_sc":
+                    self._dgrad(cs, dy, d["gin"], bn_next=self._bn_into(j), sc=(ds, d["dys"]))
+                else:
                     self._dgrad(ds, d["dys"], d["dxs"])
-                    self._dgrad(cs, dys[0], d["gin"], res=d["dxs"], bn_next=self._bn_into(j))
+                    self._dgrad(cs, dy, d["gin"], res=d["dxs"], bn_next=self._bn_into(j), fold=fold)
             else:
-                self._dgrad(cs, dys[0], d["gin"], res=dz, bn_next=self._bn_into(j))
+                self._dgrad(cs, dy, d["gin"], res=dz, bn_next=self._bn_into(j), fold=fold)
 
     def _bn_into(self, j: int):
         """The BN whose backward consumes block j's input gradient: the previous block's output
@@ -1078,9 +698,8 @@ class HipResNetEngine:
             g = self.g0
         self._bn_bwd(sp.stem_bn, arena, g, self.a0, self.y0, self.dy0, B * p * q)
         self._wgrad(st, self.x0, self.dy0)
-        tail, self._tail_wgrad = self._tail_wgrad, None
-        for cs, x, dy, fold in tail or ():
-            self._wgrad_now(cs, x, dy, fold, scratch=(self.wino_wd2, self.wino_wpart2))
+        if self._split_tail():  # the step's tail weight gradient, beside the side stream's
+            self._wgrad_now(sp.blocks[0].convs[0], *self._grad_operands(arena, 0, 0), scratch=self.wino_tail)
 
     def backward_units(self, arena):
         """The backward pass as (unit key, thunk) in execution order. Unit keys name the

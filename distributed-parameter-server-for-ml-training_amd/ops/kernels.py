@@ -152,8 +152,8 @@ def conv_fwd2(x, wf, y, stats, ws, nb, h, w, ic, oc, k, stride, pad, kg, fin: Bn
 
 def stem_conv(x, wf, y, stats, nb, h, w, cin, cp, oc, kg, sshift=None, k=3) -> bool:
     """A 3-channel stem conv with its BN statistics (csrc/kernels/stem.hip), same operands as
-    conv_fwd2: k = 3 the CIFAR stem (3 -> 64, 3x3 / stride 1 / pad 1, direct vector-ALU conv;
-    not in deterministic mode), k = 7 the ImageNet stem (3 -> 64, 7x7 / stride 2 / pad 3,
+    conv_fwd2: k = 3 the CIFAR stem (3 -> 64, 3x3 / stride 1 / pad 1, direct vector-ALU conv),
+    k = 7 the ImageNet stem (3 -> 64, 7x7 / stride 2 / pad 3,
     224 -> 112, on the MFMA with the input patch in LDS; fp32 or bf16). False: not this shape (run
     conv_fwd2 instead)."""
     if k == 7:
@@ -166,6 +166,14 @@ def stem_conv(x, wf, y, stats, nb, h, w, cin, cp, oc, kg, sshift=None, k=3) -> b
         return False
     check(rc, "stem_conv")
     return True
+
+
+def stem_ok(nb, h, w, cin, cp, oc, kg, f32, k=3) -> bool:
+    """Whether stem_conv launches for this geometry (False: it would refuse with "not this
+    shape"), on the host alone: the entries' own shape tests (csrc/kernels/stem.hip)."""
+    if k == 7:
+        return bool(kernels().psx_stem7_ok(nb, h, w, cin, cp, oc, kg, int(bool(f32))))
+    return bool(kernels().psx_stem_ok(w, cin, cp, oc, kg, int(bool(f32))))
 
 
 class BwdStatsDesc(C.Structure):
@@ -578,6 +586,12 @@ def head_fwd_bwd(act, b, hw, c, fcw, fcb, k, labels, pooled, dlogits, dact, loss
                                    C.byref(bst) if bst is not None else None, is_f32(act), stream_ptr())
     check(min(r, 0), "head_fwd_bwd")
     return r == 1
+
+
+def head_sums_ok(c, k) -> bool:
+    """Whether head_fwd_bwd given ``bst`` and ``dact`` produces the BN-backward sums (the fused
+    per-sample head runs), on the host alone (csrc/kernels/head.hip)."""
+    return bool(kernels().psx_head_sums_ok(c, k))
 
 
 def head_wgrad(dlogits, pooled, b, k, c, dw_ptr, db_ptr, gscale, grad_fp16):

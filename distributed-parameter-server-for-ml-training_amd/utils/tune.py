@@ -4,7 +4,7 @@ bare key means "1"), read by this module and by the native planners (csrc/kernel
 set from ~50 keys to the 12 below, each exercised by a test (the A/B switches whose other side
 was measured slower, and the tile-sweep overrides of the retired sweep scripts, are gone):
 
-  engine (models/engine.py):
+  engine (models/plan.py EngineOptions.from_env):
     wino=0            direct kernels instead of Winograd (tests/test_wino_gpu.py, test_fp32_gpu.py)
     wino_bnfold=0     BN + ReLU not folded into the next Winograd conv (tests/test_wino_gpu.py)
     wino_bwdfold=0    BN-backward applies not folded (tests/test_wino_fused_gpu.py)

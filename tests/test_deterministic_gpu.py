@@ -60,7 +60,7 @@ def test_side_stream_and_segments_bit_identical(monkeypatch):
     _, lay, arena, main, imgs, labs = _setup(torch.float32)
     monkeypatch.setenv("PSX_TUNE", "wgrad_stream=1")
     _, _, _, side, _, _ = _setup(torch.float32)
-    assert main.wg_stream is None and side.wg_stream is not None
+    assert not main.plan.wgrad_stream and side.plan.wgrad_stream
     grads = []
     for eng in (main, side):
         a = arena.clone()

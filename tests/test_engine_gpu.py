@@ -5,7 +5,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from psx.models.engine import HipResNetEngine  # noqa: E402
+from psx.models.engine import EngineOptions, HipResNetEngine  # noqa: E402
 from psx.models.layout import ParamLayout  # noqa: E402
 from psx.models.resnet import ResNet18  # noqa: E402
 from psx.ops import kernels as K  # noqa: E402
@@ -118,21 +118,21 @@ def test_graph_replay_matches_eager(setup):
 def test_fused_bn_finalize_matches_separate_kernels(setup, mode):
     """Folded BN finalize gives exactly what the separate finalize kernels compute from the same
     slot sums (every BN layer, two consecutive steps). conv_epilogue: last workgroup of the
-    producing launch (engine.fuse_fin); apply (default): every workgroup of the consuming apply
-    launch (bnfin.hpp bn_fin_lds), with the backward sums from bn_bwd_reduce or from the dgrad
-    epilogue (apply_bnbwd). Also: running statistics updated exactly once per step, and the
-    block-internal apply outputs equal bn_apply with the recomputed affine.
+    producing launch (EngineOptions bn_finalize="conv"); apply (default): every workgroup of the
+    consuming apply launch (bnfin.hpp bn_fin_lds), with the backward sums from bn_bwd_reduce or from
+    the dgrad epilogue (apply_bnbwd: fuse_bnbwd, the default). One engine per mode. Also: running
+    statistics updated exactly once per step, and the block-internal apply outputs equal bn_apply
+    with the recomputed affine.
     (Whole-step gradients are not compared across paths: at random init two runs of the SAME
     path already differ by ~20% through the atomic-order noise in the statistics.)"""
-    model, layout, arena, eng, x, y = setup
+    model, layout, arena, eng0, x, y = setup
     n = 256
     imgs = torch.randint(0, 256, (n, 32, 32, 3), dtype=torch.uint8, device=DEV)
     labs = torch.randint(0, 100, (n,), dtype=torch.int32, device=DEV)
+    options = EngineOptions(deterministic=eng0.deterministic, fuse_bnbwd=mode == "apply_bnbwd",
+                            bn_finalize="conv" if mode == "conv_epilogue" else "apply")
+    eng = HipResNetEngine(model, layout, eng0.B, grad_dtype=torch.float32, options=options)
     eng.index.copy_(torch.arange(eng.B, dtype=torch.int32, device=DEV))
-    before = (eng.fin_apply, eng.fuse_fin, eng.fuse_bnbwd)
-    eng.fin_apply = mode != "conv_epilogue"
-    eng.fuse_fin = mode == "conv_epilogue"
-    eng.fuse_bnbwd = mode == "apply_bnbwd"
     a = arena.clone()
     for step in range(2):
         prev = a.clone()
@@ -179,19 +179,17 @@ def test_fused_bn_finalize_matches_separate_kernels(setup, mode):
                 K.bn_apply(d["y"][i], eng.bn[bs.name]["affine"], want, bs.c, relu=True)
                 torch.cuda.synchronize()
                 assert torch.equal(want, d["a"][i]), (mode, step, bs.name)
-    eng.fin_apply, eng.fuse_fin, eng.fuse_bnbwd = before
 
 
 def test_dgrad_fused_bn_backward_sums_match_reduce_kernel(setup):
-    """engine.fuse_bnbwd: the BN-backward slot sums produced in the dgrad epilogue equal what the
-    separate bn_bwd_reduce pass computes from the stored dgrad output."""
+    """EngineOptions fuse_bnbwd (the default): the BN-backward slot sums produced in the dgrad
+    epilogue equal what the separate bn_bwd_reduce pass computes from the stored dgrad output."""
     model, layout, arena, eng, x, y = setup
     n = 256
     imgs = torch.randint(0, 256, (n, 32, 32, 3), dtype=torch.uint8, device=DEV)
     labs = torch.randint(0, 100, (n,), dtype=torch.int32, device=DEV)
     eng.index.copy_(torch.arange(eng.B, dtype=torch.int32, device=DEV))
-    before = eng.fuse_bnbwd
-    eng.fuse_bnbwd = True
+    assert eng.opts.fuse_bnbwd
     a = arena.clone()
     eng.train_step(a, imgs, labs)
     torch.cuda.synchronize()
@@ -217,7 +215,6 @@ def test_dgrad_fused_bn_backward_sums_match_reduce_kernel(setup):
     got = _slot_sums(eng._red(bs, "bwd"), bs.c, eng.deterministic)
     want = _slot_sums(ref, bs.c, eng.deterministic)
     assert torch.allclose(got, want, rtol=1e-3, atol=1e-3 * want.abs().max().item()), bs.name
-    eng.fuse_bnbwd = before
     assert checked == 8
 
 

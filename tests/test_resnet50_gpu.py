@@ -132,7 +132,7 @@ def test_resnet50_fp32_step_matches_torch_fp64():
     arena = arena.to(DEV)
     eng = HipResNetEngine(model, layout, B, grad_dtype=torch.float32, in_hw=(224, 224), dtype=torch.float32,
                           deterministic=True)
-    assert {"layer1.0.conv2", "layer3.1.conv2", "layer4.1.conv2"} <= set(eng.wino_layers), sorted(eng.wino_layers)
+    assert {"layer1.0.conv2", "layer3.1.conv2", "layer4.1.conv2"} <= set(eng.plan.wino_names()), eng.plan.wino_names()
     x = torch.randn(B, 3, 224, 224, device=DEV)
     y = torch.randint(0, 1000, (B,), device=DEV)
     eng.unpack(arena)

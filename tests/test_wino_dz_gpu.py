@@ -246,8 +246,12 @@ THREE_LAUNCH = {8: ["layer3.0.conv2", "layer3.1.conv1", "layer3.1.conv2"],
                      "layer4.1.conv2"]}
 
 
-def _step(monkeypatch, tune, B, deterministic=True):
-    from psx.models.engine import HipResNetEngine
+def _step(monkeypatch, tune, B, deterministic=True, **opts):
+    """One eager step of a fresh engine under PSX_TUNE=``tune``; ``opts`` override fields of the
+    EngineOptions that environment gives."""
+    from dataclasses import replace
+
+    from psx.models.engine import EngineOptions, HipResNetEngine
     from psx.models.layout import ParamLayout
     from psx.models.resnet import ResNet18
 
@@ -263,7 +267,8 @@ def _step(monkeypatch, tune, B, deterministic=True):
         monkeypatch.setenv("PSX_TUNE", tune)
     else:
         monkeypatch.delenv("PSX_TUNE", raising=False)
-    eng = HipResNetEngine(model, layout, B, dtype=torch.float32, deterministic=deterministic)
+    options = replace(EngineOptions.from_env(True, (32, 32), deterministic), **opts)
+    eng = HipResNetEngine(model, layout, B, dtype=torch.float32, options=options)
     eng.index.copy_(torch.arange(B, dtype=torch.int32, device=DEV))
     eng.train_step(arena0.clone(), imgs, labs)
     torch.cuda.synchronize()
@@ -295,10 +300,10 @@ def test_engine_step_fold_vs_unfolded(B, deterministic, monkeypatch):
     from .test_fp32_gpu import PT_FLOOR, STEP_FLOOR, STEP_MED_FLOOR
     e1, layout, o1 = _step(monkeypatch, "", B, deterministic)
     e0, _, o0 = _step(monkeypatch, "wino_bwdfold=0", B, deterministic)
-    assert sorted(e1.wino_dz) == sorted(e0.wino_dz) == THREE_LAUNCH[B]
-    folded = [n for n in THREE_LAUNCH[B] if n in e1._bwd_fold]
+    assert sorted(e1.plan.dz_names()) == sorted(e0.plan.dz_names()) == THREE_LAUNCH[B]
+    folded = [n for n in THREE_LAUNCH[B] if n in e1.plan.bwd_fold_names()]
     assert folded and not any(n.endswith(".0.conv2") for n in folded), folded  # behind a BN pair: no fold
-    assert not e0._bwd_fold
+    assert not e0.plan.bwd_fold_names()
     if deterministic:
         assert o1[0][0] == o0[0][0]
     errs = _per_tensor(layout, o1[0][1], o0[0][1])
@@ -313,40 +318,30 @@ def test_engine_side_stream_keeps_old_launches(monkeypatch):
     plain transform on the compute stream reproduces bit for bit (deterministic mode)."""
     B = 8
     es, _, os_ = _step(monkeypatch, "wgrad_stream=1,wino_bwdfold=0", B)
-    assert es.wg_stream is not None and not es.wino_dz
+    assert es.plan.wgrad_stream and es.wg_stream is not None and not es.plan.dz_names()
     ed, _, od = _step(monkeypatch, "wgrad_stream=1", B)
-    assert not ed.wino_dz and not any(n in ed._bwd_fold for n in THREE_LAUNCH[B]), ed._bwd_fold.keys()
+    assert not ed.plan.dz_names() and not any(n in ed.plan.bwd_fold_names() for n in THREE_LAUNCH[B]), \
+        ed.plan.bwd_fold_names()
     em, _, om = _step(monkeypatch, "wgrad_stream=0,wino_bwdfold=0", B)
-    assert em.wg_stream is None and sorted(em.wino_dz) == THREE_LAUNCH[B]
+    assert not em.plan.wgrad_stream and em.wg_stream is None and sorted(em.plan.dz_names()) == THREE_LAUNCH[B]
     assert os_[0][0] == om[0][0]
     assert torch.equal(bits(os_[0][1]), bits(om[0][1]))
     # and with every fold on: the main-stream engine folds the three-launch layers, the side-stream
     # one writes their dy; the same bytes
     ef, _, of = _step(monkeypatch, "wgrad_stream=0", B)
-    assert any(n in ef._bwd_fold for n in THREE_LAUNCH[B])
+    assert any(n in ef.plan.bwd_fold_names() for n in THREE_LAUNCH[B])
     assert torch.equal(bits(od[0][1]), bits(of[0][1]))
 
 
 def test_engine_three_launch_fold_bit_equal(monkeypatch):
-    """The three-launch layers' fold alone (the engine's other folds switched off by hand): the
-    step equals the unfolded one bit for bit, loss and gradient bytes (deterministic mode)."""
-    from psx.models import engine as E
-
+    """The three-launch layers' fold alone (EngineOptions bwd_fold="dz_only": the engine's other
+    folds off): the step equals the unfolded one bit for bit, loss and gradient bytes
+    (deterministic mode)."""
     B = 32
     _, _, o0 = _step(monkeypatch, "wino_bwdfold=0", B)
-    orig = E.HipResNetEngine._bn_bwd_to
-
-    def only_dz(self, cs, *a, **kw):
-        keep = self.bwd_fold
-        self.bwd_fold = keep and cs.name in self.wino_dz
-        try:
-            return orig(self, cs, *a, **kw)
-        finally:
-            self.bwd_fold = keep
-
-    monkeypatch.setattr(E.HipResNetEngine, "_bn_bwd_to", only_dz)
-    e1, _, o1 = _step(monkeypatch, "", B)
-    assert sorted(e1._bwd_fold) == ["layer3.1.conv1", "layer3.1.conv2", "layer4.1.conv1"], e1._bwd_fold.keys()
+    e1, _, o1 = _step(monkeypatch, "", B, bwd_fold="dz_only")
+    assert sorted(e1.plan.bwd_fold_names()) == ["layer3.1.conv1", "layer3.1.conv2", "layer4.1.conv1"], \
+        e1.plan.bwd_fold_names()
     assert o1[0][0] == o0[0][0]
     assert torch.equal(bits(o1[0][1]), bits(o0[0][1]))
 
@@ -355,7 +350,7 @@ def test_engine_deterministic_steps_repeat(monkeypatch):
     """Two identical steps (a fresh engine each: an engine carries the BN statistics' shift from
     step to step) in deterministic mode: the same loss and gradient bytes."""
     e, _, a = _step(monkeypatch, "", 8, deterministic=True)
-    assert e.wino_dz and any(n in e._bwd_fold for n in e.wino_dz)
+    assert e.plan.dz_names() and any(n in e.plan.bwd_fold_names() for n in e.plan.dz_names())
     _, _, b = _step(monkeypatch, "", 8, deterministic=True)
     assert a[0][0] == b[0][0]
     assert torch.equal(bits(a[0][1]), bits(b[0][1]))

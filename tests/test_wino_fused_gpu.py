@@ -299,7 +299,7 @@ def test_engine_bwd_fold_matches_unfolded(monkeypatch):
         a = arena0.clone()
         eng.train_step(a, imgs, labs)
         torch.cuda.synchronize()
-        assert bool(eng._bwd_fold) == (fold == "1"), eng._bwd_fold.keys()
+        assert bool(eng.plan.bwd_fold_names()) == (fold == "1"), eng.plan.bwd_fold_names()
         out[fold] = (eng.loss.double().mean().item(), eng.grads.double().clone())
     (l1, g1), (l0, g0) = out["1"], out["0"]
     assert l1 == l0  # the forward is untouched

@@ -167,7 +167,7 @@ def test_engine_step_wino_vs_direct(monkeypatch):
     for wino in ("1", "0"):
         monkeypatch.setenv("PSX_TUNE", f"wino={wino}")
         eng = HipResNetEngine(model, layout, B, dtype=torch.float32, deterministic=True)
-        assert (len(eng.wino_layers) > 0) == (wino == "1")
+        assert (len(eng.plan.wino_names()) > 0) == (wino == "1")
         eng.index.copy_(torch.arange(B, dtype=torch.int32, device=DEV))
         a = arena.clone()
         eng.train_step(a, imgs, labs)
@@ -269,7 +269,7 @@ def test_engine_bn_fold_matches_unfolded(monkeypatch):
     for fold in ("1", "0"):
         monkeypatch.setenv("PSX_TUNE", f"wino_bnfold={fold}")
         eng = HipResNetEngine(model, layout, B, dtype=torch.float32, deterministic=True)
-        assert (len(eng.wino_bnfold) == 8) == (fold == "1"), eng.wino_bnfold
+        assert (len(eng.plan.bnfold) == 8) == (fold == "1"), eng.plan.bnfold
         eng.index.copy_(torch.arange(B, dtype=torch.int32, device=DEV))
         a = arena0.clone()
         eng.train_step(a, imgs, labs)
