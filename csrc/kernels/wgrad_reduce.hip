@@ -213,9 +213,12 @@ using namespace psx;
 extern "C" {
 
 static int reduce2_cw(int OC, int IC) {
-  // chunk width: widest of 64/32/16 channels that still gives >= 1024 workgroups
+  // chunk width: from min(IC, 64) halved while it is above 16 and either does not divide IC (the
+  // grid is IC / CW chunks) or gives < 1024 workgroups. IC >= 64: the widest of 64 / 32 / 16 that
+  // divides IC (16 always does, IC % 16 == 0). IC < 64: IC, IC / 2 or IC / 4 (IC 48: 48, 24 or
+  // 12), each a divisor of IC and a multiple of 4, which is all the kernel needs.
   int CW = IC < 64 ? IC : 64;
-  while (CW > 16 && (long)OC * (IC / CW) < 1024) CW >>= 1;
+  while (CW > 16 && (IC % CW || (long)OC * (IC / CW) < 1024)) CW >>= 1;
   return CW;
 }
 

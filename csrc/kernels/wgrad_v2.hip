@@ -884,6 +884,8 @@ int route_wgrad(const WGeom& g, bool f32, WRoute& r) {
       r.pix = pow2 ? 64 : 56;
       wplan3(r, OC, IC, Kg, npix, r.pix);
     } else {
+      // (the tile kernel decodes a column as tap = chunk >> log2(IC / 8), as the fp32 one does)
+      if (IC % 8 || (IC & (IC - 1))) return -2;
       // Tile: the round-5 sweep (profiles/r5_r50_wgrad_tiles.jsonl, ResNet-50's 1x1 layers): 64 (k) x
       // 128 (oc) wins by 10-20 % on every layer up to 28x28 with OC % 128 == 0 (128x512x28 42.0 ->
       // 34.7 us, 1024x2048x14/s2 64.3 -> 55.4), 64x64 on the 56x56 ones (the model's choice there).
