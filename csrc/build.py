@@ -49,7 +49,11 @@ def _run(cmd):
 # per-source extra flags. wino_fused.hip: no SLP vectorization — packed f32 VALU (v_pk_add /
 # v_pk_fma) in the transform that runs beside the other wave's MFMAs measured slower (32x32x64
 # forward 52.2 -> 50.7 us without it; MI355X_MICROARCH.md: packed f32 beside MFMAs is an anti-lever)
-FILE_FLAGS = {"wino_fused.hip": ["-fno-slp-vectorize"], "wino_wgrad.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
+FILE_FLAGS = {"wino_fused.hip": ["-fno-slp-vectorize"], "wino_wgrad.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
+              # muon.hip: packed fp32 VALU off. With it on the compiler emits 116 v_pk_add / v_pk_mul / v_pk_fma_f32 in
+              # the slab sums and epilogues that run beside the MFMAs (the anti-lever named above); the results are
+              # the same bits either way, and the update is MFMA- and LDS-bound, so no speed is claimed for it
+              "muon.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def kernel_flags(opt, src=None) -> list:

@@ -129,6 +129,14 @@ _KERNEL_SIGS = {
     "psx_lamb_apply_multi": (i32, [vp, vp, i32, i32, vp, vp, vp, i64, vp, i32, i32, vp, vp, f32, f32, f32, f64, f64,
                                    f64, i64, vp, vp]),
     "psx_lamb_apply": (i32, [vp, vp, vp, vp, i64, vp, i32, i32, vp, vp, f32, f32, f32, f64, f64, f64, i64, vp, vp]),
+    "psx_muon_seg_size": (i32, []),
+    "psx_muon_tile": (i32, []),
+    "psx_muon_ktile": (i32, []),
+    "psx_muon_apply_multi": (i32, [vp, vp, i32, i32, vp, vp, i64, vp, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32,
+                                   i32, f32, f32, f32, i32, vp, vp]),
+    "psx_muon_apply": (i32, [vp, vp, vp, i64, vp, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32, i32, f32, f32, f32,
+                             i32, vp, vp]),
+    "psx_muon_orthogonalize": (i32, [vp, vp, i64, vp, i32, i32, vp, vp, vp, i32, f32, f32, f32, i32, vp]),
     "psx_dc_apply": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, i32, i32, vp, vp]),
     "psx_dc_fetch_copy": (i32, [vp, vp, vp, i64, i64, vp]),
     "psx_guard_chunk": (i32, []),

@@ -993,6 +993,160 @@ def lamb_apply(p, stage, m, v, table: LarsTable, lr, t, gscale=1.0, wd=0.0, beta
           "lamb_apply")
 
 
+MUON_COEF = (3.4445, -4.7750, 2.0315)  # the Newton-Schulz polynomial of Jordan et al. 2024
+MUON_TILE, MUON_KTILE = 64, 32  # kMuTile, kMuKT in csrc/kernels/muon.hip
+_MUON_SEG = [("offset", "<i8"), ("xoff", "<i8"), ("aoff", "<i8"), ("boff", "<i8"), ("rows", "<i4"), ("cols", "<i4"),
+             ("m", "<i4"), ("n", "<i4"), ("mp", "<i4"), ("np", "<i4"), ("slabs", "<i4"), ("kslab", "<i4"),
+             ("lars", "<i4"), ("tall", "<i4")]  # MuonSeg
+
+
+class _MuonPlan(C.Structure):
+    """csrc/kernels/muon.hip MuonPlan."""
+    _fields_ = [("segs", C.c_void_p), ("mat_of", C.c_void_p), ("map_a", C.c_void_p), ("map_b", C.c_void_p),
+                ("map_n", C.c_void_p), ("x0", C.c_void_p), ("x1", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p),
+                ("nmat", C.c_int), ("nta", C.c_int), ("ntb", C.c_int), ("ntn", C.c_int)]
+
+
+class MuonTable:
+    """What the Newton-Schulz chain of the Muon update needs on the device, built once per layout
+    (csrc/kernels/muon.hip): one MuonSeg record per tensor of ``lars`` with ndim > 1 (its shape,
+    its m <= n working orientation, both padded to the 64 tile, the K split of A = X X^T and its
+    places in the workspaces), the three tile maps {matrix, ti, tj, slab} of the grouped launches,
+    and the zeroed workspaces: the X ping-pong, A (one m x m slab per K slab) and B.
+
+    The K split: a matrix with few output tiles and a long K (512 x 4608: 36 upper tiles) is cut
+    into 2 slabs of at least 256 while tiles x slabs stays under about 512 workgroups. Every slab
+    is read again by B's staging, so more slabs cost more than they fill: whole update on ResNet-18
+    / ResNet-50 with at most 1, 2, 3, 4, 8 slabs 1197 / 2575, 1150 / 2515, 1279 / 2618, 1330 / 2816,
+    1798 / 2928 us (profiles/muon_kernels.txt; PSX_TUNE mu_slabs=N sets the cap for such runs)."""
+
+    def __init__(self, layout, device, lars: LarsTable):
+        import numpy as np
+
+        ents = sorted((e for e in layout.entries.values() if e.region == "param" and e.numel > 0),
+                      key=lambda e: e.offset)
+        assert [e.name for e in ents] == lars.names, "muon_table: not the LARS table's layout"
+        T, KT = MUON_TILE, MUON_KTILE
+        cap = int(tune("mu_slabs") or 2)
+        mats = [(t, e) for t, e in enumerate(ents) if len(e.shape) > 1]
+        assert mats, "muon_table: no tensor with ndim > 1"
+        rec = np.zeros(len(mats), dtype=_MUON_SEG)
+        mat_of = np.full(len(ents), -1, dtype=np.int32)
+        maps = ([], [], [])
+        xoff = aoff = boff = 0
+        for k, (t, e) in enumerate(mats):
+            rows = int(e.shape[0])
+            cols = int(e.numel) // rows
+            assert rows * cols == e.numel and e.numel < 2 ** 31, f"muon_table: {e.name}"
+            m, n = min(rows, cols), max(rows, cols)
+            mp, np_ = -(-m // T) * T, -(-n // T) * T
+            tm, tn = mp // T, np_ // T
+            upper = tm * (tm + 1) // 2
+            ktiles = np_ // KT
+            per = -(-ktiles // max(1, min(-(-512 // upper), cap, np_ // 256)))
+            slabs = -(-ktiles // per)
+            rec[k] = (e.offset, xoff, aoff, boff, rows, cols, m, n, mp, np_, slabs, per * KT, t, int(rows > cols))
+            mat_of[t] = k
+            tri = [(k, i, j) for i in range(tm) for j in range(i, tm)]
+            maps[0].extend(ij + (s,) for s in range(slabs) for ij in tri)
+            maps[1].extend(ij + (0,) for ij in tri)
+            maps[2].extend((k, i, j, 0) for i in range(tm) for j in range(tn))
+            xoff, aoff, boff = xoff + mp * np_, aoff + slabs * mp * mp, boff + mp * mp
+        self.device = lars.device
+        self.lars = lars
+        self.nmat = len(mats)
+        self.seg = rec
+        if self.device.type == "cuda":
+            assert kernels().psx_muon_seg_size() == rec.dtype.itemsize, "MuonSeg layout"
+            assert (kernels().psx_muon_tile(), kernels().psx_muon_ktile()) == (T, KT), "kMuTile / kMuKT"
+        dev = self.device
+        self.dev = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
+        self.mat_of = torch.from_numpy(mat_of).to(dev)
+        self.maps = [torch.tensor(mp_, dtype=torch.int32).reshape(-1, 4).to(dev) for mp_ in maps]
+        self.x = [torch.zeros(xoff, dtype=torch.float32, device=dev) for _ in range(2)]
+        self.a = torch.zeros(aoff, dtype=torch.float32, device=dev)
+        self.b = torch.zeros(boff, dtype=torch.float32, device=dev)
+        self.plan = _MuonPlan(ptr(self.dev), ptr(self.mat_of), ptr(self.maps[0]), ptr(self.maps[1]), ptr(self.maps[2]),
+                              ptr(self.x[0]), ptr(self.x[1]), ptr(self.a), ptr(self.b), self.nmat,
+                              *[int(mp_.shape[0]) for mp_ in self.maps])
+
+    def flops(self, steps=5) -> float:
+        """The nominal multiply-adds x 2 of ``steps`` iterations of the algorithm: 2 m^2 n + 2 m^3
+        + 2 m^2 n per matrix and iteration. Not what the MFMAs execute: the two SYRK forms run
+        only the tiles on or above the diagonal, and every matrix is padded to the tile."""
+        return float(steps * sum(4.0 * s["m"] ** 2 * s["n"] + 2.0 * s["m"] ** 3 for s in self.seg))
+
+
+def _muon_common(p, stage, buf, table, mtable, momentum, steps, img, n, what):
+    n = _stage_common(p, stage, table, buf, img, n, what)
+    assert mtable.lars is table, f"{what}: the MuonTable of another LarsTable"
+    assert int(steps) >= 1, f"{what} steps"
+    assert (buf is not None) == bool(momentum), f"{what}: the momentum buffer goes with momentum != 0"
+    assert len({p.data_ptr(), stage.data_ptr(), buf.data_ptr() if buf is not None else 0}) == 3, \
+        f"{what}: p, stage, buf alias"
+    return n
+
+
+def muon_apply_multi(p, srcs, stage, buf, table: LarsTable, mtable: MuonTable, lr, aux_lr=0.0, gscale=1.0,
+                     momentum=0.0, wd=0.0, steps=5, coef=MUON_COEF, normalize=True, n=None, img=None):
+    """The Muon server update from the W gathered wires (csrc/kernels/muon.hip): s = sum_k srcs[k]
+    (fp32, list order, as sgd_apply_multi forms it; left in ``stage``), g = gscale * s, buf =
+    momentum * buf + g, u = g + momentum * buf (``buf`` None with momentum 0: u = g). Every tensor
+    of ``table`` with ndim > 1, as its rows x cols matrix U: X = U / (|U|_F + 1e-7) (transposed when
+    rows > cols), ``steps`` times A = X X^T, B = b A + c A A, X = a X + B X with (a, b, c) =
+    ``coef``, then p = p * (1 - lr * wd) - lr * sqrt(max(1, rows / cols)) * X; the 1-D ones p -=
+    aux_lr * u (aux_lr 0: lr). ``table.ratios`` receives |U|_F, ``img`` (bf16) the image of the
+    updated parameters. All sources fp16 or all fp32; at most 32. 1 + 3 * steps + 1 launches on
+    the current stream, no host synchronisation."""
+    n = _muon_common(p, stage, buf, table, mtable, momentum, steps, img, n, "muon_apply_multi")
+    state = (p, stage) + ((buf,) if buf is not None else ())
+    arr, fp16 = _wire_srcs(srcs, n, p.device, state, "muon_apply_multi")
+    a, b, c = coef
+    check(kernels().psx_muon_apply_multi(ptr(p), arr, len(srcs), int(fp16), ptr(stage), ptr(buf), n, ptr(table.dev),
+                                         table.ntensors, table.nblocks, ptr(table.partials), ptr(table.ratios),
+                                         C.addressof(mtable.plan), float(lr), float(aux_lr or lr), float(gscale),
+                                         float(momentum), float(wd), int(steps), float(a), float(b), float(c),
+                                         int(bool(normalize)), ptr(img), stream_ptr()), "muon_apply_multi")
+
+
+def muon_apply(p, stage, buf, table: LarsTable, mtable: MuonTable, lr, aux_lr=0.0, gscale=1.0, momentum=0.0, wd=0.0,
+               steps=5, coef=MUON_COEF, normalize=True, n=None, img=None):
+    """muon_apply_multi for a gradient sum that is already dense fp32 in ``stage`` (decoded q8 /
+    sign1 / top-k payloads, an accumulated round); ``stage`` is left as it is."""
+    n = _muon_common(p, stage, buf, table, mtable, momentum, steps, img, n, "muon_apply")
+    a, b, c = coef
+    check(kernels().psx_muon_apply(ptr(p), ptr(stage), ptr(buf), n, ptr(table.dev), table.ntensors, table.nblocks,
+                                   ptr(table.partials), ptr(table.ratios), C.addressof(mtable.plan), float(lr),
+                                   float(aux_lr or lr), float(gscale), float(momentum), float(wd), int(steps), float(a),
+                                   float(b), float(c), int(bool(normalize)), ptr(img), stream_ptr()), "muon_apply")
+
+
+def muon_orthogonalize(mats, steps=5, coef=MUON_COEF, normalize=True) -> list:
+    """The Newton-Schulz chain of the Muon update alone (csrc/kernels/muon.hip) on a list of 2-D
+    fp32 device tensors, all in one grouped run: for each U, X = U / (|U|_F + 1e-7) when
+    ``normalize`` (else U), transposed when rows > cols, ``steps`` times A = X X^T, B = b A + c A A,
+    X = a X + B X; returns the results in the inputs' shapes."""
+    from types import SimpleNamespace as NS
+
+    assert mats and all(m.dim() == 2 and m.dtype == torch.float32 and m.device.type == "cuda" for m in mats), \
+        "muon_orthogonalize mats"
+    entries, off = {}, 0
+    for i, m in enumerate(mats):
+        entries[i] = NS(name=str(i), region="param", offset=off, numel=m.numel(), shape=tuple(m.shape))
+        off += m.numel()
+    layout = NS(entries=entries, param_numel=off)
+    table = LarsTable(layout, mats[0].device)
+    mtable = MuonTable(layout, mats[0].device, table)
+    src = torch.cat([m.reshape(-1) for m in mats])
+    out = torch.empty_like(src)
+    a, b, c = coef
+    check(kernels().psx_muon_orthogonalize(ptr(src), ptr(out), off, ptr(table.dev), table.ntensors, table.nblocks,
+                                           ptr(table.partials), ptr(table.ratios), C.addressof(mtable.plan), int(steps),
+                                           float(a), float(b), float(c), int(bool(normalize)), stream_ptr()),
+          "muon_orthogonalize")
+    return [out[e.offset:e.offset + e.numel].view(e.shape) for e in entries.values()]
+
+
 def _dc_f32(t, n, dev, what):
     assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n and t.device == dev, what
 

@@ -1,14 +1,15 @@
 """The server's update rules: what ParameterServer.update_range (parallel/server.py) runs.
 
-One rule per update form: SGD (momentum and weight decay included), LARS, AdamW, LAMB, and the
+One rule per update form: SGD (momentum and weight decay included), LARS, AdamW, LAMB, Muon, and the
 gradient guard, a wrapper that ends in the SGD rule. ``rule_of(cfg)`` picks the server's one rule.
 A rule holds no state: it reads and writes the server it is handed (params, momentum_buf, adam_m /
-adam_v / adam_t, agg, _lars_tab, _guard_state, ...). Its parts:
+adam_v / adam_t, agg, _lars_tab, _muon_tab, _guard_state, ...). Its parts:
 
 * ``whole``: the rule needs a norm over the whole arena before the first element moves, so the
   entry refuses a partial range with ``refusal``;
 * ``adam``: the rule counts its updates in adam_t and keeps both moments (checkpoint / resume);
 * ``table``: the rule keeps per-tensor ratios (the device segment table, ops/kernels.py LarsTable);
+* ``matrix``: the rule runs a matrix chain per weight tensor (its workspaces, ops/kernels.py MuonTable);
 * ``scatters(cfg)``: a top-k payload may be scattered straight into the parameters;
 * ``device_payload(s, codec, payloads, weight, img)``: the device form that decodes q8 / sign1
   payloads inside the update (the wrapper parallel/pushcodec.py names); None unless defined;
@@ -102,7 +103,7 @@ def _scalars(fn: str, *a, **hp):
 
 class Rule:
     """The parts of a rule that have a default (the module docstring lists them all)."""
-    whole, adam, table, refusal = False, False, False, ""
+    whole, adam, table, matrix, refusal = False, False, False, False, ""
     device_payload = None  # the in-kernel decode of q8 / sign1 payloads, where the rule has one
 
     def scatters(self, cfg) -> bool:
@@ -306,7 +307,70 @@ class LAMB(AdamW):
         return {"lamb": _adam_metrics(s), "lamb_trust_ratio": s.lamb_trust_ratios()}
 
 
-_OPTIMIZERS = {"sgd": SGD(), "lars": LARS(), "adamw": AdamW(), "lamb": LAMB()}
+class Muon(Rule):
+    """--optimizer muon (Jordan et al. 2024), update number t: s = the fp32 sum of the wires in list
+    order, g = weight * s. Momentum, Nesterov form, every element: b = mu * b + g, u = g + mu * b
+    (mu = --momentum, b = momentum_buf, zeros at the start; mu = 0: u = g and no buffer). Tensors
+    with ndim > 1, read as the row-major rows x cols matrix U they are in the arena: X = U /
+    (|U|_F + 1e-7), transposed if rows > cols so that m <= n; --muon-ns-steps times A = X X^T, B =
+    b A + c A A, X = a X + B X with (a, b, c) = (3.4445, -4.7750, 2.0315); O = X in the tensor's own
+    orientation; w = w (1 - lr wd) - lr sqrt(max(1, rows / cols)) O. 1-D tensors: w -= lr_aux * u,
+    no weight decay (--muon-aux-lr, 0 = lr). --warmup-steps scales lr and lr_aux alike. Device:
+    the 1 + 3 * steps + 1 launches of csrc/kernels/muon.hip, fp32 operands on the exact-fp32 MFMA;
+    CPU arena: the same formula in torch fp32, tensor by tensor (equal to a tolerance, not bit for
+    bit: the summation orders differ)."""
+    whole = table = matrix = True
+    refusal = ("--optimizer muon orthogonalises whole weight matrices, and needs every one's norm before its first "
+               "element moves: a partial range [{lo}, {hi}) of {n} cannot be applied (no bucketed or sharded updates)")
+
+    @staticmethod
+    def aux_lr(s) -> float:
+        aux, base = float(s.cfg.muon_aux_lr), s._base_lr
+        return aux * (s.lr / base) if aux and base else s.lr
+
+    def device(self, s, srcs, weight, lo, hi, img, summed):
+        s._ratios_applied = True
+        stage(s, srcs, "muon", s.momentum_buf, s._lars_tab, s._muon_tab, lr=s.lr, aux_lr=self.aux_lr(s), gscale=weight,
+              momentum=s.cfg.momentum, wd=s.cfg.weight_decay, steps=s.cfg.muon_ns_steps, n=s.n, img=img)
+
+    def host(self, s, srcs, weight, lo, hi, summed):
+        cfg = s.cfg
+        s._ratios_applied = True
+        stage_host(s, srcs)
+        a, b, c = K.MUON_COEF
+        lr, aux, mu = float(np.float32(s.lr)), float(np.float32(self.aux_lr(s))), float(np.float32(cfg.momentum))
+        u = s.agg * float(np.float32(weight))
+        if s.momentum_buf is not None:
+            s.momentum_buf.mul_(mu).add_(u)
+            u = u + mu * s.momentum_buf
+        norms = []
+        for e in _param_entries(s):
+            w = s.params[e.offset:e.offset + e.numel]
+            ue = u[e.offset:e.offset + e.numel]
+            if len(e.shape) <= 1:
+                w.sub_(aux * ue)
+                continue
+            rows = int(e.shape[0])
+            U = ue.view(rows, -1)
+            nrm = float(U.double().norm())
+            norms.append(nrm)
+            X = U * float(np.float32(1.0 / (nrm + 1e-7)))
+            X = X.t() if rows > U.shape[1] else X
+            for _ in range(int(cfg.muon_ns_steps)):
+                A = X @ X.t()
+                X = a * X + (b * A + c * (A @ A)) @ X
+            O = X.t() if rows > U.shape[1] else X
+            step = float(np.float32(lr) * np.sqrt(np.float32(max(1.0, rows / U.shape[1]))))
+            w.mul_(float(np.float32(1.0) - np.float32(lr) * np.float32(cfg.weight_decay))).sub_(step * O.reshape(-1))
+        s._muon_norms = norms
+
+    def metrics(self, s) -> dict:
+        return {"muon": {"ns_steps": int(s.cfg.muon_ns_steps), "momentum": float(s.cfg.momentum),
+                         "aux_lr": float(s.cfg.muon_aux_lr)},
+                "muon_update_norm": trust_ratios(s, Muon, s._muon_norms)}
+
+
+_OPTIMIZERS = {"sgd": SGD(), "lars": LARS(), "adamw": AdamW(), "lamb": LAMB(), "muon": Muon()}
 _GUARD = Guard()
 
 

@@ -67,7 +67,9 @@ class ParameterServer:
         # --optimizer lars / lamb: per-tensor ratios, in the device segment table + scratch
         # (ops/kernels.py LarsTable) or, on a CPU arena, the last update's list of the adapted tensors
         self._lars_tab = K.lars_table(layout, self.device) if self.rule.table and self.device.type == "cuda" else None
-        self._lars_ratios = self._lamb_ratios = None
+        # --optimizer muon: the Newton-Schulz tile maps and workspaces (ops/kernels.py MuonTable)
+        self._muon_tab = K.MuonTable(layout, self.device, self._lars_tab) if self.rule.matrix and self._lars_tab else None
+        self._lars_ratios = self._lamb_ratios = self._muon_norms = None
         self._ratios_applied = False
         # --optimizer adamw / lamb: both moments and the count of completed updates
         self.adam_m = torch.zeros_like(self.params) if self.rule.adam else None

@@ -12,7 +12,8 @@ Keeps every flag and environment variable of the reference with the same default
 and adds the MI355X-native knobs: --gpus/--nproc, --codec {none,fp16,q8,sign1,topk},
 --topk-ratio,
 --dtype, --momentum/--weight-decay (server optimizer, default 0 = reference parity),
---optimizer {sgd,lars,adamw,lamb} with --lars-trust/--lars-eps and --adam-beta1/--adam-beta2/--adam-eps,
+--optimizer {sgd,lars,adamw,lamb,muon} with --lars-trust/--lars-eps, --adam-beta1/--adam-beta2/--adam-eps and
+--muon-ns-steps/--muon-aux-lr,
 --warmup-steps (linear lr warmup of the server update),
 --dc-lambda/--dc-adaptive (async delay compensation), --clip-norm/--skip-nonfinite (global-norm clipping, non-finite guard), --model,
 --synthetic, --ckpt-every/--resume, --sync-semantics {barrier,reference}, --topology.
@@ -88,6 +89,12 @@ class PSConfig:
     # wd w of every tensor with ndim > 1; 1-D tensors take ratio 1 and no weight decay (the lars
     # convention). No clamp on |w|, no global gradient normalisation. Scope as lars: the Python
     # server's whole-arena updates only; momentum must be 0.
+    # muon (csrc/kernels/muon.hip, Jordan et al. 2024): Nesterov momentum (momentum, 0 = none), and for
+    # every tensor with ndim > 1 the update orthogonalised by muon_ns_steps Newton-Schulz iterations
+    # on its rows x cols matrix, with the decoupled weight decay; 1-D tensors take the plain momentum
+    # step with muon_aux_lr (0 = lr) and no weight decay. Scope as lars.
+    muon_ns_steps: int = 5
+    muon_aux_lr: float = 0.0
     # warmup_steps N > 0: update number k (1-based) runs with lr * min(1, k / N); 0 = constant lr.
     # Python server only: the native loops and the graph round hold a fixed lr.
     warmup_steps: int = 0
@@ -166,8 +173,8 @@ class PSConfig:
             raise ValueError(f"--codec must be none, fp16, q8, sign1 or topk, got {self.codec!r}")
         if self.topology not in ("colocated", "dedicated", "sharded"):
             raise ValueError(f"--topology must be colocated, dedicated or sharded, got {self.topology!r}")
-        if self.optimizer not in ("sgd", "lars", "adamw", "lamb"):
-            raise ValueError(f"--optimizer must be sgd, lars, adamw or lamb, got {self.optimizer!r}")
+        if self.optimizer not in ("sgd", "lars", "adamw", "lamb", "muon"):
+            raise ValueError(f"--optimizer must be sgd, lars, adamw, lamb or muon, got {self.optimizer!r}")
         if self.optimizer in ("adamw", "lamb"):
             opt = f"--optimizer {self.optimizer}"
             if not (0.0 <= self.adam_beta1 < 1.0) or not (0.0 <= self.adam_beta2 < 1.0):
@@ -180,6 +187,13 @@ class PSConfig:
             raise ValueError("--warmup-steps must be >= 0")
         if self.optimizer == "lars" and (not (self.lars_trust > 0.0) or self.lars_eps < 0.0):
             raise ValueError("--optimizer lars: --lars-trust must be > 0 and --lars-eps >= 0")
+        if self.optimizer == "muon":
+            if int(self.muon_ns_steps) < 1:
+                raise ValueError("--optimizer muon: --muon-ns-steps must be >= 1")
+            if not self.muon_aux_lr >= 0.0:
+                raise ValueError("--optimizer muon: --muon-aux-lr must be >= 0")
+            if not (0.0 <= self.momentum < 1.0):
+                raise ValueError("--optimizer muon: --momentum must be in [0, 1)")
         if self.dc_lambda < 0.0:
             raise ValueError("--dc-lambda must be >= 0")
         if self.dc_adaptive and not self.dc_lambda > 0.0:
@@ -202,7 +216,7 @@ class PSConfig:
             if self.dc_lambda > 0.0:
                 raise ValueError("--clip-norm / --skip-nonfinite run on the SGD server update: not with --dc-lambda")
         if self.whole_arena_update:
-            # a shard boundary or a gradient bucket may split a tensor (lars, lamb); no shard sees the
+            # a shard boundary or a gradient bucket may split a tensor (lars, lamb, muon); no shard sees the
             # whole gradient, and a bucket is applied before the others have arrived (the guard)
             who, one_server, at_once = (f"--optimizer {self.optimizer}", "needs whole tensors on one server",
                                         "updates the whole arena at once")
@@ -274,9 +288,9 @@ class PSConfig:
     @property
     def whole_arena_update(self) -> bool:
         """The server update needs a norm over the whole arena (every tensor's for --optimizer lars
-        / lamb, the whole gradient's for the gradient guard) before the first element moves: no
+        / lamb / muon, the whole gradient's for the gradient guard) before the first element moves: no
         --topology sharded, no --overlap."""
-        return self.optimizer in ("lars", "lamb") or self.grad_guard
+        return self.optimizer in ("lars", "lamb", "muon") or self.grad_guard
 
     @property
     def grad_guard(self) -> bool:
@@ -321,12 +335,16 @@ def add_arguments(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
       help="worker compute precision: fp32 (reference, default) or bf16 (fast path)")
     A("--momentum", type=float, default=None)
     A("--weight-decay", type=float, default=None)
-    A("--optimizer", choices=["sgd", "lars", "adamw", "lamb"], default=None,
+    A("--optimizer", choices=["sgd", "lars", "adamw", "lamb", "muon"], default=None,
       help="server optimizer: sgd (default), lars (layer-wise trust ratio on tensors with ndim > 1; "
            "uses --momentum / --weight-decay; Python server, whole-arena updates), adamw (Adam with "
            "decoupled --weight-decay; Python server, also bucketed and sharded rounds) or lamb (the Adam "
            "moments with a per-tensor ratio |w| / |update| on tensors with ndim > 1; Python server, "
-           "whole-arena updates)")
+           "whole-arena updates) or muon (Nesterov --momentum, orthogonalised per weight matrix by Newton-Schulz "
+           "iterations; decoupled --weight-decay; Python server, whole-arena updates)")
+    A("--muon-ns-steps", type=int, default=None, help="Muon: Newton-Schulz iterations per update (default 5)")
+    A("--muon-aux-lr", type=float, default=None,
+      help="Muon: learning rate of the 1-D tensors (BN, biases); 0 = --lr (default)")
     A("--lars-trust", type=float, default=None, help="LARS trust coefficient (default 0.001)")
     A("--lars-eps", type=float, default=None, help="LARS denominator epsilon (default 1e-8)")
     A("--adam-beta1", type=float, default=None, help="AdamW / LAMB first-moment decay (default 0.9)")

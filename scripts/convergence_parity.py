@@ -30,6 +30,9 @@
 * ``psx_fp32_lamb``   psx_fp32 with the LAMB server optimizer (--optimizer lamb, lr ``--lamb-lr``, default
                       0.01, weight decay 1e-2, fp16 wire), its own run like the AdamW curve: compared
                       with ``psx_fp32`` (``lamb_vs_psx_fp32``), not a parity claim and not asserted.
+* ``psx_fp32_muon``   psx_fp32 with the Muon server optimizer (--optimizer muon, lr ``--muon-lr``, default
+                      0.02, momentum 0.95, weight decay 0.01, five Newton-Schulz steps, fp16 wire),
+                      its own run: compared with ``psx_fp32`` (``muon_vs_psx_fp32``), not asserted.
 * ``psx_fp32_lars_warmup`` ``psx_fp32_lars`` with a linear lr warmup over ``--warmup-steps`` updates
                       (default 50): whether the warmup closes the LARS curve's gap to plain SGD
                       (``lars_warmup_vs_psx_fp32``).
@@ -217,6 +220,7 @@ def main():
     ap.add_argument("--skip-w4", action="store_true")
     ap.add_argument("--lars-lr", type=float, default=2.0, help="lr of the psx_fp32_lars curve")
     ap.add_argument("--lamb-lr", type=float, default=0.01, help="lr of the psx_fp32_lamb curve")
+    ap.add_argument("--muon-lr", type=float, default=0.02, help="lr of the psx_fp32_muon curve")
     ap.add_argument("--warmup-steps", type=int, default=50, help="warmup of the psx_fp32_lars_warmup curve")
     ap.add_argument("--only", default="", help="comma-separated subset of the curves to run (default: all)")
     args = ap.parse_args()
@@ -227,6 +231,7 @@ def main():
     lars = dict(optimizer="lars", lr=args.lars_lr, momentum=0.9, weight_decay=5e-4)
     adamw = dict(optimizer="adamw", lr=1e-3, weight_decay=1e-2)
     lamb = dict(optimizer="lamb", lr=args.lamb_lr, weight_decay=1e-2)
+    muon = dict(optimizer="muon", lr=args.muon_lr, momentum=0.95, weight_decay=0.01)
     lars_wu = dict(lars, warmup_steps=args.warmup_steps)
     only = [x for x in args.only.split(",") if x]
     for name, fn in (("torch_fp32", lambda: run_torch(args, train, test, 0)),
@@ -239,6 +244,7 @@ def main():
                      ("psx_fp32_lars", lambda: run_psx(args, train, test, "fp32", "fp16", **lars)),
                      ("psx_fp32_adamw", lambda: run_psx(args, train, test, "fp32", "fp16", **adamw)),
                      ("psx_fp32_lamb", lambda: run_psx(args, train, test, "fp32", "fp16", **lamb)),
+                     ("psx_fp32_muon", lambda: run_psx(args, train, test, "fp32", "fp16", **muon)),
                      ("psx_fp32_lars_warmup", lambda: run_psx(args, train, test, "fp32", "fp16", **lars_wu)),
                      ("psx_bf16", lambda: run_psx(args, train, test, "bf16", "fp16")),
                      ("psx_fp32_reference_bn", lambda: run_psx(args, train, test, "fp32", "fp16", bn_sync=False))):
@@ -261,7 +267,7 @@ def main():
         print(f"  vs torch_fp32: {name:18s} {json.dumps(cmp[name])}", flush=True)
     vs_psx = {}
     for name in ("psx_fp32_q8", "psx_fp32_sign1", "psx_fp32_q8delta", "psx_fp32_lars", "psx_fp32_adamw",
-                 "psx_fp32_lamb", "psx_fp32_lars_warmup"):
+                 "psx_fp32_lamb", "psx_fp32_muon", "psx_fp32_lars_warmup"):
         if name not in runs or "psx_fp32" not in runs:
             continue
         d = smooth(runs[name]["loss"], args.window) - smooth(runs["psx_fp32"]["loss"], args.window)
@@ -283,7 +289,7 @@ def main():
            "sign1_vs_psx_fp32": vs_psx.get("psx_fp32_sign1"),
            "q8delta_vs_psx_fp32": vs_psx.get("psx_fp32_q8delta"),
            "lars_vs_psx_fp32": vs_psx.get("psx_fp32_lars"), "adamw_vs_psx_fp32": vs_psx.get("psx_fp32_adamw"),
-           "lamb_vs_psx_fp32": vs_psx.get("psx_fp32_lamb"),
+           "lamb_vs_psx_fp32": vs_psx.get("psx_fp32_lamb"), "muon_vs_psx_fp32": vs_psx.get("psx_fp32_muon"),
            "lars_warmup_vs_psx_fp32": vs_psx.get("psx_fp32_lars_warmup"),
            "w4_sync": w4}
     with open(os.path.join(args.out, "convergence_parity.json"), "w") as f:
