@@ -137,6 +137,12 @@ _KERNEL_SIGS = {
     "psx_muon_apply": (i32, [vp, vp, vp, i64, vp, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32, i32, f32, f32, f32,
                              i32, vp, vp]),
     "psx_muon_orthogonalize": (i32, [vp, vp, i64, vp, i32, i32, vp, vp, vp, i32, f32, f32, f32, i32, vp]),
+    "psx_powersgd_seg_size": (i32, []),
+    "psx_powersgd_plan_size": (i32, []),
+    "psx_powersgd_lds_floats": (i32, []),
+    "psx_powersgd_header_bytes": (i32, []),
+    "psx_powersgd_encode": (i32, [vp, i32, vp, i64, vp, i32, vp, i32, vp, vp, i64, vp, vp]),
+    "psx_powersgd_decode": (i32, [vp, i32, i64, vp, i64, vp, i32, vp, i32, i32, vp]),
     "psx_dc_apply": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, i32, i32, vp, vp]),
     "psx_dc_fetch_copy": (i32, [vp, vp, vp, i64, i64, vp]),
     "psx_guard_chunk": (i32, []),

@@ -1338,3 +1338,129 @@ def augment(img, labels, index, out, out_labels, b, h, w, pad, seed, step_dev, t
 
 def nchw_to_nhwc(x, y, n, c, h, w, cp):
     check(kernels().psx_nchw_to_nhwc(ptr(x), ptr(y), n, c, h, w, cp, is_f32(y), stream_ptr()), "nchw_to_nhwc")
+
+
+POWERSGD_RANKS = (4, 8, 12, 16)  # a rank step is one v_mfma_f32_16x16x4_f32
+POWERSGD_TILE, POWERSGD_KTILE, POWERSGD_KSLAB = 64, 32, 256  # kPgTile, kPgKT; columns per slab of psgd_project
+POWERSGD_LDS_FLOATS = 32768  # kPgLdsFloats in csrc/kernels/powersgd.hip
+POWERSGD_HEADER = 16  # kPgHeader
+_PSGD_SEG = [("offset", "<i8"), ("numel", "<i8"), ("foff", "<i8"), ("woff", "<i8"), ("rows", "<i4"), ("cols", "<i4"),
+             ("slabs", "<i4"), ("kslab", "<i4"), ("comp", "<i4"), ("vec", "<i4")]  # PsgdSeg
+
+
+class _PsgdPlan(C.Structure):
+    """csrc/kernels/powersgd.hip PsgdPlan."""
+    _fields_ = [("segs", C.c_void_p), ("map_p", C.c_void_p), ("map_q", C.c_void_p), ("map_r", C.c_void_p),
+                ("map_t", C.c_void_p), ("comp", C.c_void_p), ("factors", C.c_long), ("tails", C.c_long),
+                ("wsfloats", C.c_long), ("nseg", C.c_int), ("ncomp", C.c_int), ("ntp", C.c_int), ("ntq", C.c_int),
+                ("ntr", C.c_int), ("ntt", C.c_int), ("orth_floats", C.c_int)]
+
+
+class PowerSGDTable:
+    """What the PowerSGD codec (csrc/kernels/powersgd.hip) needs of a layout at one rank, on the
+    worker and on the server alike; immutable, so one table serves every codec of a process. One
+    PsgdSeg record per trainable tensor in arena order. A tensor with ndim > 1, read as the
+    row-major rows x cols matrix it is in the arena (as MuonTable reads it), is compressed when
+    rank * (rows + cols) < rows * cols and rows * rank fits psgd_orth's LDS budget; every other
+    tensor goes to the fp16 tail. Payload: [16-byte frame | fp32 factors | fp16 tail], padded to
+    16 bytes; a compressed tensor's factors are P^ [rows][rank] then Q' [cols][rank]. The columns
+    of a compressed tensor are cut into slabs of 256 for psgd_project (512 x 4608: 8 row tiles x 18
+    slabs), whose partial products fill the workspace. On a CPU device only the host records
+    (``seg``) and the sizes exist."""
+
+    def __init__(self, layout, device, rank: int):
+        import numpy as np
+
+        rank = int(rank)
+        assert rank in POWERSGD_RANKS, f"powersgd rank must be one of {POWERSGD_RANKS}, got {rank}"
+        ents = sorted((e for e in layout.entries.values() if e.region == "param" and e.numel > 0),
+                      key=lambda e: e.offset)
+        assert ents, "powersgd_table: no trainable tensors"
+        T, KS = POWERSGD_TILE, POWERSGD_KSLAB
+        rec = np.zeros(len(ents), dtype=_PSGD_SEG)
+        maps = ([], [], [], [])
+        comp = []
+        foff = toff = woff = end = orth = 0
+        for t, e in enumerate(ents):
+            assert e.offset == end and e.numel < 2 ** 31, f"powersgd_table: {e.name} leaves a gap or is too large"
+            end = e.offset + e.numel
+            rows = int(e.shape[0]) if len(e.shape) > 1 else 1
+            cols = int(e.numel) // rows
+            if len(e.shape) > 1 and rank * (rows + cols) < rows * cols and rows * rank <= POWERSGD_LDS_FLOATS:
+                slabs = -(-cols // KS)
+                rec[t] = (e.offset, e.numel, foff, woff, rows, cols, slabs, KS, 1,
+                          int(e.offset % 4 == 0 and cols % 4 == 0))
+                tm, tn = -(-rows // T), -(-cols // T)
+                maps[0].extend((t, i, s, 0) for i in range(tm) for s in range(slabs))
+                maps[1].extend((t, j, len(comp), 0) for j in range(tn))
+                maps[2].extend((t, i, j, 0) for i in range(tm) for j in range(tn))
+                comp.append(t)
+                foff += rank * (rows + cols)
+                woff += slabs * rows * rank
+                orth = max(orth, rows * rank)
+            else:
+                rec[t] = (e.offset, e.numel, toff, 0, rows, cols, 0, 0, 0, 0)
+                maps[3].extend((t, c, 0, 0) for c in range(-(-e.numel // LARS_CHUNK)))
+                toff += e.numel
+        assert end == layout.param_numel, "powersgd_table: the tensors do not cover the trainable prefix"
+        self.rank, self.n = rank, int(layout.param_numel)
+        self.seg, self.comp = rec, comp
+        self.factors, self.tails, self.wsfloats = int(foff), int(toff), int(woff)
+        self.payload_bytes = (POWERSGD_HEADER + 4 * self.factors + 2 * self.tails + 15) & ~15
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            return
+        k = kernels()
+        assert k.psx_powersgd_seg_size() == rec.dtype.itemsize, "PsgdSeg layout"
+        assert k.psx_powersgd_plan_size() == C.sizeof(_PsgdPlan), "PsgdPlan layout"
+        assert (k.psx_powersgd_lds_floats(), k.psx_powersgd_header_bytes()) == (POWERSGD_LDS_FLOATS, POWERSGD_HEADER), \
+            "kPgLdsFloats / kPgHeader"
+        dev = self.device
+        self.dev = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
+        self.maps = [torch.tensor(m, dtype=torch.int32).reshape(-1, 4).to(dev) for m in maps]
+        self.comp_dev = torch.tensor(comp, dtype=torch.int32, device=dev)
+        self.plan = _PsgdPlan(ptr(self.dev), *[ptr(m) if m.numel() else None for m in self.maps],
+                              ptr(self.comp_dev) if comp else None, self.factors, self.tails, self.wsfloats,
+                              len(ents), len(comp), *[int(m.shape[0]) for m in self.maps], int(orth))
+
+    def workspace(self) -> torch.Tensor:
+        """A zeroed workspace of one encoder: the slabs' partial P, then the dropped-column masks."""
+        return torch.zeros(self.wsfloats + len(self.comp), dtype=torch.float32, device=self.device)
+
+
+def _psgd_payload_ok(table: PowerSGDTable, payload) -> bool:
+    return (payload.dtype == torch.uint8 and payload.is_contiguous() and payload.numel() == table.payload_bytes
+            and payload.device == table.dev.device)
+
+
+def powersgd_encode(g, resid, q, payload, ws, table: PowerSGDTable):
+    """One PowerSGD push (csrc/kernels/powersgd.hip): M = g + resid per compressed tensor, P = M Q,
+    P^ = Gram-Schmidt of P, Q' = M^T P^ into ``payload`` and ``q`` (fp32 [table.factors], the
+    factor section's layout), resid = M - P^ Q'^T; the other tensors as fp16 of ``g`` into the
+    payload's tail. ``g``: fp16 or fp32, >= n elements. Four launches on the current stream."""
+    n = table.n
+    assert g.dtype in _GRAD_DTYPES and g.is_contiguous() and g.numel() >= n and g.device == table.dev.device, \
+        "powersgd_encode g"
+    assert resid.dtype == torch.float32 and resid.is_contiguous() and resid.numel() == n and resid.device == g.device, \
+        "powersgd_encode resid"
+    assert q.dtype == torch.float32 and q.is_contiguous() and q.numel() == max(1, table.factors) \
+        and q.device == g.device, "powersgd_encode q"
+    assert ws.dtype == torch.float32 and ws.numel() >= table.wsfloats + len(table.comp) and ws.device == g.device, \
+        "powersgd_encode ws"
+    assert _psgd_payload_ok(table, payload), "powersgd_encode payload"
+    check(kernels().psx_powersgd_encode(ptr(g), int(g.dtype == torch.float16), ptr(resid), n, ptr(table.dev),
+                                        len(table.seg), C.addressof(table.plan), table.rank, ptr(q), ptr(payload),
+                                        payload.numel(), ptr(ws), stream_ptr()), "powersgd_encode")
+
+
+def powersgd_decode(payloads, out, table: PowerSGDTable, add=False):
+    """out = [out +] the sum of the decoded payloads (at most 32) in list order, fp32: per
+    compressed tensor sum_w P^_w Q'_w^T, the fp16 tails summed in fp32. One launch."""
+    n = table.n
+    assert 1 <= len(payloads) <= 32 and all(_psgd_payload_ok(table, p) for p in payloads), "powersgd_decode payloads"
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n and out.device == table.dev.device, \
+        "powersgd_decode out"
+    arr = (C.c_void_p * len(payloads))(*[p.data_ptr() for p in payloads])
+    check(kernels().psx_powersgd_decode(arr, len(payloads), table.payload_bytes, ptr(out), n, ptr(table.dev),
+                                        len(table.seg), C.addressof(table.plan), table.rank, int(bool(add)),
+                                        stream_ptr()), "powersgd_decode")

@@ -6,13 +6,15 @@ runner and the server ask instead of telling the codecs apart themselves.
     topk   (index, fp16 value) pairs, int32  parallel/topk.py
     q8     block-scaled int8, uint8          parallel/q8.py
     sign1  block-scaled sign bits, uint8     parallel/sign1.py
+    powersgd  rank-r factors + fp16 tail, uint8   parallel/powersgd.py
 
 An entry answers: ``wire_dtype``; ``slot``, the receive buffer of one push; ``empty``, the
 contribution of a rank with no gradient; ``encoder``, the worker's error-feedback encoder or None;
 ``reducible``, whether a reduce can sum the wire (else it is gathered); ``wire_bytes``, the bytes one
 push moves; ``decode``, the payload into dense fp32; ``in_kernel``, the name of the ops/kernels.py
 wrapper that decodes such payloads inside the update (``Rule.device_payload``), or None. ``ratio``
-is ``--topk-ratio``; only top-k reads it.
+is ``--topk-ratio``, which only top-k reads; for powersgd it is the ``powersgd.Binding`` (layout,
+rank, seed) the codec is bound to (``arg_of`` picks the one of a configuration).
 
 ``of_payload`` recognises a pushed tensor on the host, never by reading a device header back: a
 server takes whatever codec a push arrives in, whatever it is configured for.
@@ -21,7 +23,7 @@ from __future__ import annotations
 
 import torch
 
-from . import blockwire, q8, sign1, topk
+from . import blockwire, powersgd, q8, sign1, topk
 
 
 class Dense:
@@ -44,6 +46,12 @@ class Dense:
 
     def decode(self, payload, n: int, out: torch.Tensor, add: bool = False, ratio=None) -> torch.Tensor:
         return out.add_(payload[:n].to(torch.float32)) if add else out.copy_(payload[:n])
+
+    def decode_all(self, payloads, n: int, out: torch.Tensor, ratio=None) -> torch.Tensor:
+        """out = the fp32 sum of the decoded payloads in list order."""
+        for i, p in enumerate(payloads):
+            self.decode(p, n, out, i > 0, ratio)
+        return out
 
 
 class TopK(Dense):
@@ -90,25 +98,62 @@ class Block(Dense):
         return self.wire.decode(payload, n, out=out, add=add)
 
 
+class LowRank(Dense):
+    """PowerSGD factors (parallel/powersgd.py); ``ratio`` is the powersgd.Binding of every call."""
+    reducible, wire_dtype = False, torch.uint8
+
+    def __init__(self, name: str):
+        self.name = name
+
+    def slot(self, n, device, ratio=None):
+        return torch.empty(powersgd.payload_bytes(ratio.layout, ratio.rank), dtype=self.wire_dtype, device=device)
+
+    def empty(self, n, device, ratio=None):
+        return powersgd.empty_payload(ratio.layout, ratio.rank, device)
+
+    def encoder(self, n, device, ratio=None):
+        return powersgd.PowerSGDCodec(ratio.layout, ratio.rank, device, ratio.seed)
+
+    def wire_bytes(self, t, n):
+        return t.numel()
+
+    def decode(self, payload, n, out, add=False, ratio=None):
+        return powersgd.decode([payload], out, ratio.layout, ratio.rank, add)
+
+    def decode_all(self, payloads, n, out, ratio=None):
+        return powersgd.decode(payloads, out, ratio.layout, ratio.rank)  # one launch for the W payloads
+
+
 CODECS = {"none": Dense("none", torch.float32), "fp16": Dense("fp16", torch.float16),
           "topk": TopK("topk", torch.int32),
           "q8": Block("q8", q8, q8.Q8Codec, "q8_apply_multi"),
-          "sign1": Block("sign1", sign1, sign1.Sign1Codec, "sign1_apply_multi")}
+          "sign1": Block("sign1", sign1, sign1.Sign1Codec, "sign1_apply_multi"),
+          "powersgd": LowRank("powersgd")}
 _BLOCK = (CODECS["q8"], CODECS["sign1"])
 
 
+def arg_of(cfg, layout):
+    """What the entries' calls take as ``ratio`` under this configuration."""
+    if cfg.codec == "powersgd":
+        return powersgd.Binding(layout, cfg.powersgd_rank, cfg.seed)
+    return cfg.topk_ratio
+
+
 def is_payload(t: torch.Tensor) -> bool:
-    """A top-k or block-wire payload, which no reduce can sum, not a dense wire."""
+    """A top-k, block-wire or powersgd payload, which no reduce can sum, not a dense wire."""
     return t.dtype == torch.int32 or t.dtype == torch.uint8
 
 
-def of_payload(t: torch.Tensor, n: int, prefer: str | None = None):
-    """The codec of a pushed tensor for n parameters: int32 is top-k; uint8 is a block wire, told by
-    its byte length, the ``prefer``-red (configured) codec's first where an arena of a few elements
-    gives both the same; anything else is the dense wire of its dtype."""
+def of_payload(t: torch.Tensor, n: int, prefer: str | None = None, ratio=None):
+    """The codec of a pushed tensor for n parameters: int32 is top-k; uint8 is a powersgd payload
+    when its byte length is that of the bound layout (``ratio`` a powersgd.Binding), else a block
+    wire, told by its byte length, the ``prefer``-red (configured) codec's first where an arena of a
+    few elements gives both the same; anything else is the dense wire of its dtype."""
     if t.dtype == torch.int32:
         return CODECS["topk"]
     if t.dtype == torch.uint8:
+        if isinstance(ratio, powersgd.Binding) and t.numel() == powersgd.payload_bytes(ratio.layout, ratio.rank):
+            return CODECS["powersgd"]
         own = CODECS.get(prefer)
         for c in ((own,) if own in _BLOCK else ()) + _BLOCK:
             if t.numel() == c.wire.payload_bytes(n):

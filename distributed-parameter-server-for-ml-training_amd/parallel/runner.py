@@ -679,7 +679,7 @@ def _server_rounds(cfg, server, chan, steps, device, skip, t, ctx):
             chan.drain()
         return
     # rank 0's contribution: zeros to a reduce, an empty payload to a gather
-    zeros = pushcodec.CODECS[cfg.codec].empty(server.n, device, cfg.topk_ratio)
+    zeros = pushcodec.CODECS[cfg.codec].empty(server.n, device, pushcodec.arg_of(cfg, server.layout))
     zbuf = torch.zeros(server.layout.buffer_numel, dtype=torch.float32, device=device) if cfg.bn_sync else None
     skip_b = rounds_to_batches(skip, steps, K)  # checkpointed rounds -> batches (window aligned)
     done = skip_b

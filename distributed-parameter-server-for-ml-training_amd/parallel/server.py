@@ -61,6 +61,8 @@ class ParameterServer:
         self._mom_first = True
         # the one update rule of this server (parallel/rules.py): update_range runs it on every route
         self.rule = R.rule_of(cfg)
+        # what the push codec's calls take beside n: --topk-ratio, or the powersgd binding of this layout
+        self._codec_arg = PC.arg_of(cfg, layout)
         # fp32 aggregation buffer: whole-arena rules stage every round's sum through it; otherwise
         # allocated when a path first needs it (in-process sync rounds, decoded payloads)
         self.agg = torch.zeros(self.n, dtype=torch.float32, device=self.device) if self.rule.whole else None
@@ -162,11 +164,11 @@ class ParameterServer:
 
     def codec_of(self, t: torch.Tensor):
         """The push codec (parallel/pushcodec.py) of a pushed tensor, the configured one preferred."""
-        return PC.of_payload(t, self.n, self.cfg.codec)
+        return PC.of_payload(t, self.n, self.cfg.codec, self._codec_arg)
 
     def _dense_of(self, t: torch.Tensor, out: torch.Tensor | None = None, add: bool = False):
         """out = [out +] the dense fp32 gradient of a push of any codec (default: the aggregation buffer)."""
-        return self.codec_of(t).decode(t, self.n, self._agg() if out is None else out, add, self.cfg.topk_ratio)
+        return self.codec_of(t).decode(t, self.n, self._agg() if out is None else out, add, self._codec_arg)
 
     # ------------------------------------------------------------------ the one update entry
     _IMG_OF_WIRE = object()
@@ -195,8 +197,7 @@ class ParameterServer:
         if not codec.reducible:
             if on_device and codec.in_kernel is not None and rule.device_payload is not None:
                 return rule.device_payload(self, codec, srcs, weight, img)
-            for i, p in enumerate(srcs):
-                self._dense_of(p, add=i > 0)
+            codec.decode_all(srcs, self.n, self._agg(), self._codec_arg)
             srcs, summed = [self.agg], True
         if on_device:
             rule.device(self, srcs, weight, lo, hi, img, summed)
@@ -659,7 +660,7 @@ class ParameterServer:
         finished = set()
         n = self.n
         own = PC.CODECS[self.cfg.codec]
-        slots = {w: own.slot(n, self.device, self.cfg.topk_ratio) for w in rank_of}
+        slots = {w: own.slot(n, self.device, self._codec_arg) for w in rank_of}
         # one fetch snapshot per worker (codec wire buffers): an in-flight send never races the
         # next update of the arena
         from .codec import FetchCodec

@@ -369,12 +369,15 @@ class Worker:
         # top-k (parallel/topk.py), block-scaled int8 (parallel/q8.py) or 1-bit sign
         # (parallel/sign1.py); None = dense wire
         self.encoder = pushcodec.CODECS[cfg.codec].encoder(compute.layout.param_numel,
-                                                           getattr(compute, "device", "cpu"), cfg.topk_ratio)
+                                                           getattr(compute, "device", "cpu"),
+                                                           pushcodec.arg_of(cfg, compute.layout))
 
     # ---------------------------------------------------------------- reference API
     def connect_to_server(self):
         self.worker_id, self.total_workers = self.channel.register(self.worker_name, self.requested_id)
         self.log(f"Registered as Worker {self.worker_id} (Total workers: {self.total_workers})")
+        if hasattr(self.encoder, "bind_worker"):  # --codec powersgd draws its Q per worker id
+            self.encoder.bind_worker(self.worker_id)
         if hasattr(self.channel, "bind_compute"):  # e.g. the sharded round pads the gradient wire
             self.channel.bind_compute(self.compute)
         wire = self.channel.weight_wire() if hasattr(self.channel, "weight_wire") else None

@@ -9,8 +9,8 @@ Keeps every flag and environment variable of the reference with the same default
   worker  --server (env PARAMETER_SERVER_ADDRESS, localhost:8000), --worker-name,
           --epochs 3, --batch-size 128, --lr 0.1, --sync-steps 1
 
-and adds the MI355X-native knobs: --gpus/--nproc, --codec {none,fp16,q8,sign1,topk},
---topk-ratio,
+and adds the MI355X-native knobs: --gpus/--nproc, --codec {none,fp16,q8,sign1,topk,powersgd},
+--topk-ratio, --powersgd-rank {4,8,12,16},
 --dtype, --momentum/--weight-decay (server optimizer, default 0 = reference parity),
 --optimizer {sgd,lars,adamw,lamb,muon} with --lars-trust/--lars-eps, --adam-beta1/--adam-beta2/--adam-eps and
 --muon-ns-steps/--muon-aux-lr,
@@ -63,7 +63,9 @@ class PSConfig:
     topology: str = "colocated"    # colocated: rank 0 = PS + worker 0; dedicated: rank 0 = PS only;
     #                                sharded: every rank = worker + 1/world of the PS (parallel/sharded.py)
     codec: str = "fp16"            # none (fp32 wire) | fp16 (reference) | q8 (block-scaled int8) | sign1 (1 bit) | topk
+    #                                | powersgd (rank-r factors of every weight matrix, parallel/powersgd.py)
     topk_ratio: float = 0.01
+    powersgd_rank: int = 4         # 4, 8, 12 or 16: a rank step is one v_mfma_f32_16x16x4_f32
     # compute dtype of the HIP engine: fp32 = the reference's training precision (worker.py:333-348;
     # exact-f32 MFMA), bf16 = the fast path (bf16 operands, fp32 accumulation and master weights)
     dtype: str = "fp32"
@@ -170,7 +172,7 @@ class PSConfig:
         if self.eval_workers not in ("all", "first"):
             raise ValueError("--eval-workers must be all or first")
         if self.codec not in _push_codecs():
-            raise ValueError(f"--codec must be none, fp16, q8, sign1 or topk, got {self.codec!r}")
+            raise ValueError(f"--codec must be none, fp16, q8, sign1, topk or powersgd, got {self.codec!r}")
         if self.topology not in ("colocated", "dedicated", "sharded"):
             raise ValueError(f"--topology must be colocated, dedicated or sharded, got {self.topology!r}")
         if self.optimizer not in ("sgd", "lars", "adamw", "lamb", "muon"):
@@ -267,6 +269,10 @@ class PSConfig:
             raise ValueError("--synthetic-kind must be proto or hard")
         if not (0.0 < self.topk_ratio <= 1.0):
             raise ValueError("--topk-ratio must be in (0, 1]")
+        if int(self.powersgd_rank) not in (4, 8, 12, 16):
+            raise ValueError("--powersgd-rank must be 4, 8, 12 or 16")
+        if self.codec == "powersgd" and self.overlap is True:
+            raise ValueError("--codec powersgd encodes the whole gradient at once: not with --overlap")
         if self.fault_inject.startswith("crash_in_push") and self.mode != "async":
             # only the async native channel can die between its PUSH request and the transfer
             raise ValueError("--fault-inject crash_in_push applies to --mode async (native event loop) only")
@@ -275,7 +281,7 @@ class PSConfig:
     def resolve_overlap(self, world: int) -> bool:
         """--overlap / --no-overlap, or auto: bucketed rounds when there are peers to exchange
         with and the round qualifies (sync, one push per batch, dense wire, rank-0 server). The
-        error-feedback codecs (q8, sign1, topk) encode the whole gradient at once, and a whole-arena update
+        error-feedback codecs (q8, sign1, topk, powersgd) encode the whole gradient at once, and a whole-arena update
         (whole_arena_update) cannot start before the last bucket: no bucketed rounds. --optimizer
         adamw is element-wise and stays eligible. --fetch-codec q8delta encodes the final arena of a
         round, which a bucketed round broadcasts piecewise before it exists: no bucketed rounds."""
@@ -328,9 +334,12 @@ def add_arguments(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
     A("--topology", choices=["colocated", "dedicated", "sharded"], default=None)
     A("--codec", choices=list(_push_codecs()), default=None,
       help="gradient wire: fp16 cast (reference, default), none (fp32), q8 (block-scaled int8, 1.016 B/param), "
-           "sign1 (1-bit sign + a scale per 256, 0.1406 B/param) or topk; q8, sign1 and topk keep an error-feedback "
-           "residual on the worker")
+           "sign1 (1-bit sign + a scale per 256, 0.1406 B/param), topk or powersgd (rank-r factors of every weight "
+           "matrix, about 0.055 B/param at rank 4); q8, sign1, topk and powersgd keep an error-feedback residual on "
+           "the worker")
     A("--topk-ratio", type=float, default=None)
+    A("--powersgd-rank", type=int, choices=[4, 8, 12, 16], default=None,
+      help="--codec powersgd: columns of the two factors per weight matrix (default 4)")
     A("--dtype", choices=["fp32", "bf16"], default=None,
       help="worker compute precision: fp32 (reference, default) or bf16 (fast path)")
     A("--momentum", type=float, default=None)

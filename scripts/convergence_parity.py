@@ -15,6 +15,8 @@
                       torch seed-to-seed spread.
 * ``psx_fp32_sign1``  the same with the 1-bit sign wire and error feedback (--codec sign1); compared
                       against ``psx_fp32`` in the same way (``sign1_vs_psx_fp32``).
+* ``psx_fp32_powersgd`` the same with the rank-4 PowerSGD wire and error feedback (--codec powersgd);
+                      compared against ``psx_fp32`` (``powersgd_vs_psx_fp32``), recorded and not asserted.
 * ``psx_fp32_q8delta`` psx_fp32 with the delta-quantised int8 fetch wire (--fetch-codec q8delta): the worker
                       computes on the server's shadow, not on the fp32 master; compared against
                       ``psx_fp32`` (``q8delta_vs_psx_fp32``), next to the torch seed-to-seed spread,
@@ -240,6 +242,7 @@ def main():
                      ("psx_fp32_wire32", lambda: run_psx(args, train, test, "fp32", "none")),
                      ("psx_fp32_q8", lambda: run_psx(args, train, test, "fp32", "q8")),
                      ("psx_fp32_sign1", lambda: run_psx(args, train, test, "fp32", "sign1")),
+                     ("psx_fp32_powersgd", lambda: run_psx(args, train, test, "fp32", "powersgd")),
                      ("psx_fp32_q8delta", lambda: run_psx(args, train, test, "fp32", "fp16", fetch_codec="q8delta")),
                      ("psx_fp32_lars", lambda: run_psx(args, train, test, "fp32", "fp16", **lars)),
                      ("psx_fp32_adamw", lambda: run_psx(args, train, test, "fp32", "fp16", **adamw)),
@@ -266,7 +269,7 @@ def main():
                      "test_acc_diff_pp": r["test_acc"] - runs["torch_fp32"]["test_acc"]}
         print(f"  vs torch_fp32: {name:18s} {json.dumps(cmp[name])}", flush=True)
     vs_psx = {}
-    for name in ("psx_fp32_q8", "psx_fp32_sign1", "psx_fp32_q8delta", "psx_fp32_lars", "psx_fp32_adamw",
+    for name in ("psx_fp32_q8", "psx_fp32_sign1", "psx_fp32_powersgd", "psx_fp32_q8delta", "psx_fp32_lars", "psx_fp32_adamw",
                  "psx_fp32_lamb", "psx_fp32_muon", "psx_fp32_lars_warmup"):
         if name not in runs or "psx_fp32" not in runs:
             continue
@@ -287,6 +290,7 @@ def main():
                                           "20% label noise, 100 classes",
            "runs": runs, "vs_torch_fp32": cmp, "q8_vs_psx_fp32": vs_psx.get("psx_fp32_q8"),
            "sign1_vs_psx_fp32": vs_psx.get("psx_fp32_sign1"),
+           "powersgd_vs_psx_fp32": vs_psx.get("psx_fp32_powersgd"),
            "q8delta_vs_psx_fp32": vs_psx.get("psx_fp32_q8delta"),
            "lars_vs_psx_fp32": vs_psx.get("psx_fp32_lars"), "adamw_vs_psx_fp32": vs_psx.get("psx_fp32_adamw"),
            "lamb_vs_psx_fp32": vs_psx.get("psx_fp32_lamb"), "muon_vs_psx_fp32": vs_psx.get("psx_fp32_muon"),
