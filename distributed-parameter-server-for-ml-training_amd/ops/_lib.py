@@ -149,6 +149,12 @@ _KERNEL_SIGS = {
     "psx_guard_state_bytes": (i32, []),
     "psx_guard_apply_multi": (i32, [vp, vp, i32, i32, vp, vp, i64, vp, vp, f32, f32, f32, f32, f32, i32, vp, vp]),
     "psx_guard_apply": (i32, [vp, vp, vp, i64, vp, vp, f32, f32, f32, f32, f32, i32, vp, vp]),
+    "psx_robust_gram_slice": (i32, []),
+    "psx_robust_state_bytes": (i32, []),
+    "psx_robust_rank": (i32, [vp, i32, i32, vp, i64, i64, i64, i32, i32, f32, vp]),
+    "psx_robust_gram": (i32, [vp, i32, i32, i64, vp, vp]),
+    "psx_robust_krum_select": (i32, [vp, i32, i32, i32, vp, vp, vp]),
+    "psx_robust_select_sum": (i32, [vp, i32, i32, vp, vp, i64, i32, f32, vp]),
 }
 
 _RUNTIME_SIGS = {

@@ -1253,6 +1253,70 @@ def guard_apply(p, stage, state: GuardState, lr, gscale=1.0, momentum=0.0, wd=0.
                                     int(first), ptr(img), stream_ptr()), "guard_apply")
 
 
+ROBUST_GRAM_SLICE = 16384  # kGramSlice in csrc/kernels/robust.hip: arena elements per workgroup, the longest fp32 chain
+ROBUST_KINDS = {"trimmed": 0, "median": 1}
+
+
+def _robust_agg(agg, n, dev, what):
+    assert agg.dtype == torch.float32 and agg.is_contiguous() and agg.numel() >= n and agg.device == dev \
+        and dev.type == "cuda", f"{what} agg"
+
+
+def robust_rank(srcs, agg, kind, trim=1, c=1.0, n=None, off=0, cnt=None):
+    """agg[off : off + cnt] = c * the coordinate-wise trimmed mean (without the ``trim`` smallest and
+    largest values; W > 2 * trim) or median of the W gathered wires (csrc/kernels/robust.hip
+    robust_rank_kernel; NaN counts as +inf). All sources fp16 or all fp32, >= n elements, at most
+    32; agg fp32 [n]. One launch on the current stream."""
+    n = agg.numel() if n is None else n
+    cnt = n - off if cnt is None else cnt
+    _robust_agg(agg, n, agg.device, "robust_rank")
+    arr, fp16 = _wire_srcs(srcs, n, agg.device, (agg,), "robust_rank")
+    check(kernels().psx_robust_rank(arr, len(srcs), int(fp16), ptr(agg), n, off, cnt, ROBUST_KINDS[kind], int(trim),
+                                    float(c), stream_ptr()), "robust_rank")
+
+
+class KrumState:
+    """The scratch and the device state block of multi-Krum for an arena of ``n`` elements: the Gram
+    partials [ceil(n / ROBUST_GRAM_SLICE)][32][32] (upper 16x16 tiles; what the kernel does not
+    write stays zero), sel [32], and the per-worker selection counters (int64 [32])."""
+
+    def __init__(self, n, device):
+        self.n = int(n)
+        assert self.n > 0, "KrumState n"
+        assert kernels().psx_robust_gram_slice() == ROBUST_GRAM_SLICE, "kGramSlice"
+        assert kernels().psx_robust_state_bytes() == 32 * 8, "RobustState layout"
+        self.nblocks = -(-self.n // ROBUST_GRAM_SLICE)
+        self.partials = torch.zeros(self.nblocks, 32, 32, dtype=torch.float32, device=device)
+        self.sel = torch.zeros(32, dtype=torch.float32, device=device)
+        self.selected = torch.zeros(32, dtype=torch.int64, device=device)
+        self.device = self.sel.device
+
+
+def robust_gram(srcs, state: KrumState):
+    """state.partials = per workgroup the fp32 Gram matrix <src_i, src_j>, i <= j, of its slice of the
+    W wires (fp16 wires on v_mfma_f32_16x16x32_f16, fp32 wires on the exact-fp32 16x16x4)."""
+    arr, fp16 = _wire_srcs(srcs, state.n, state.device, (state.partials,), "robust_gram")
+    check(kernels().psx_robust_gram(arr, len(srcs), int(fp16), state.n, ptr(state.partials), stream_ptr()),
+          "robust_gram")
+    return state.partials
+
+
+def robust_krum_select(state: KrumState, nsrc, byzantine):
+    """state.sel[k] = 1 for the nsrc - byzantine workers multi-Krum selects from state.partials (else 0);
+    their counters in state.selected go up by one. One workgroup, no host synchronisation."""
+    check(kernels().psx_robust_krum_select(ptr(state.partials), state.nblocks, int(nsrc), int(byzantine),
+                                           ptr(state.sel), ptr(state.selected), stream_ptr()), "robust_krum_select")
+    return state.sel
+
+
+def robust_select_sum(srcs, state: KrumState, agg, m, c=1.0):
+    """agg = c * fl(1 / m) * the fp32 sum in source order of the wires with state.sel[k] != 0."""
+    _robust_agg(agg, state.n, state.device, "robust_select_sum")
+    arr, fp16 = _wire_srcs(srcs, state.n, state.device, (agg,), "robust_select_sum")
+    check(kernels().psx_robust_select_sum(arr, len(srcs), int(fp16), ptr(state.sel), ptr(agg), state.n, int(m),
+                                          float(c), stream_ptr()), "robust_select_sum")
+
+
 def grad_aggregate(srcs_dev_ptrs, nsrc, src_fp16, dst, n, scale=1.0, accumulate=False):
     """srcs_dev_ptrs: int64 device tensor holding nsrc device pointers."""
     check(kernels().psx_grad_aggregate(ptr(srcs_dev_ptrs), nsrc, int(src_fp16), ptr(dst),

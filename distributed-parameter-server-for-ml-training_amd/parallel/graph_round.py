@@ -53,7 +53,7 @@ def graph_round_enabled(cfg, transport) -> bool:
             and cfg.topology == "colocated" and not cfg.momentum and not cfg.bn_sync
             # per-bucket applies: a bucket may split a tensor (lars); a captured apply would bake the
             # update number's scalars into the graph (adamw, lamb), or its lr (--warmup-steps)
-            and cfg.optimizer == "sgd" and not cfg.warmup_steps > 0
+            and cfg.optimizer == "sgd" and getattr(cfg, "aggregate", "mean") == "mean" and not cfg.warmup_steps > 0
             and not cfg.grad_guard)  # ... and no bucket sees the whole gradient's norm
 
 

@@ -81,7 +81,7 @@ def native_loop_enabled(cfg, transport) -> bool:
     adamw / lamb, the gradient guard (--clip-norm / --skip-nonfinite) and --warmup-steps are
     served by the Python loop."""
     return (os.environ.get("PSX_NATIVE_LOOP", "1") == "1" and getattr(transport, "native", False)
-            and cfg.codec in ("fp16", "none") and not cfg.bn_sync and cfg.optimizer == "sgd"
+            and cfg.codec in ("fp16", "none") and not cfg.bn_sync and cfg.optimizer == "sgd" and getattr(cfg, "aggregate", "mean") == "mean"
             and not cfg.grad_guard and not cfg.warmup_steps > 0)
 
 

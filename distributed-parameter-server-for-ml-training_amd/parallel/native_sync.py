@@ -107,6 +107,7 @@ def native_sync_enabled(cfg, transport, chan, server, rank: int) -> bool:
             and getattr(transport, "native", False) and getattr(transport, "world_size", 1) > 1
             and cfg.mode == "sync" and cfg.topology == "dedicated" and cfg.codec in ("fp16", "none")
             and cfg.optimizer == "sgd"  # the C++ rounds launch the SGD kernels: LARS / AdamW / LAMB stay in Python
+            and getattr(cfg, "aggregate", "mean") == "mean"  # ... on the wire sum: the robust combine (parallel/robust.py) too
             and not cfg.warmup_steps > 0  # ... with the lr they were started with
             and not cfg.bn_sync and type(chan) in (SyncCollectiveChannel, OverlapSyncChannel)
             and not getattr(chan, "root_worker", True) and getattr(chan, "agg_mode", "gather") == "gather"):

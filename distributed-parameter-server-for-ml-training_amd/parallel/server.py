@@ -31,6 +31,7 @@ from ..utils import trace
 from . import control as CP
 from . import fetchq8, topk
 from . import pushcodec as PC
+from . import robust as RB
 from . import rules as R
 from .core import APPLY, WAIT, ServerCore
 
@@ -72,6 +73,10 @@ class ParameterServer:
         # --optimizer muon: the Newton-Schulz tile maps and workspaces (ops/kernels.py MuonTable)
         self._muon_tab = K.MuonTable(layout, self.device, self._lars_tab) if self.rule.matrix and self._lars_tab else None
         self._lars_ratios = self._lamb_ratios = self._muon_norms = None
+        # --aggregate trimmed / median / krum (parallel/robust.py): the combine update_range puts in
+        # front of the rule; _robust_wires: the wires of an open in-process round
+        self._robust = RB.Robust(cfg, self.n, self.device) if getattr(cfg, "aggregate", "mean") != "mean" else None
+        self._robust_wires = []
         self._ratios_applied = False
         # --optimizer adamw / lamb: both moments and the count of completed updates
         self.adam_m = torch.zeros_like(self.params) if self.rule.adam else None
@@ -184,7 +189,14 @@ class ParameterServer:
         refuses a partial range. ``img``: the bf16 image slice that receives the updated range, on
         the device in the same pass (default: the weight wire's, which an ``img`` of the caller's,
         and every host form, leaves stale). Several ranges of one round share the momentum 'first
-        step' flag and the Adam update number: finish_round_apply closes the round."""
+        step' flag and the Adam update number: finish_round_apply closes the round.
+
+        --aggregate trimmed / median / krum (parallel/robust.py): two or more unsummed dense wires are
+        first combined into the aggregation buffer, agg = e * c with e the robust estimate and c =
+        fl(1 / fl(weight)), and the rule goes on with ``[agg], summed=True`` and the same weight. So
+        weight * agg is e wherever the core's weight is 1 / W; any other weight (reference
+        semantics) keeps its meaning as a scale on e. One source, or an already summed one, passes
+        through untouched; the gradient guard then sees the estimate, not the raw sum."""
         rule = self.rule
         if rule.whole and (lo, hi) != (0, self.n):
             raise ValueError(rule.refusal.format(lo=lo, hi=hi, n=self.n))
@@ -193,6 +205,10 @@ class ParameterServer:
         on_device, own_img = self.device.type == "cuda", img is not self._IMG_OF_WIRE
         if on_device and not own_img:
             img = self.wire.img[lo:hi] if self.wire is not None else None
+        if self._robust is not None and not summed and len(srcs) > 1:
+            whole = (lo, hi) == (0, self.n)
+            srcs = [self._robust.combine(srcs, self._agg() if whole else self._agg()[lo:hi], weight, whole)]
+            summed = True
         codec = self.codec_of(srcs[0])
         if not codec.reducible:
             if on_device and codec.in_kernel is not None and rule.device_payload is not None:
@@ -451,7 +467,12 @@ class ParameterServer:
                 # entries when the push counter reaches total_workers (server.py:264-288)
                 if res.decision in (WAIT, APPLY):
                     self._pending[worker_id] = self._dense_of(grads, torch.zeros(self.n, device=self.device))
-                if res.apply:
+                if res.apply and self._robust is not None:  # the entries themselves, not their sum
+                    wires = list(self._pending.values())
+                    self._pending.clear()
+                    self._update_round(wires, res.weight)
+                    self._commit_buffers()
+                elif res.apply:
                     self._dense_of(sum(self._pending.values()))
                     self._pending.clear()
                     self.apply(self.agg, res.weight)
@@ -464,6 +485,15 @@ class ParameterServer:
                 self._update_round([grads], res.weight)
                 self._commit_buffers()
                 return True
+            if self._robust is not None:  # the combine needs every wire of the round, not their running sum
+                if res.decision in (WAIT, APPLY):
+                    self._robust_wires.append(grads[: self.n].clone())
+                    self._round_count += 1
+                if res.apply:
+                    wires, self._robust_wires, self._round_count = self._robust_wires, [], 0
+                    self._update_round(wires, res.weight)
+                    self._commit_buffers()
+                return res.accepted
             if res.decision in (WAIT, APPLY):
                 self._dense_of(grads, add=self._round_count != 0)
                 self._round_count += 1
@@ -622,6 +652,8 @@ class ParameterServer:
         m["update_time_source"] = self.update_time_source
         m["optimizer"] = self.cfg.optimizer
         m.update(self.rule.metrics(self))
+        if self._robust is not None:
+            m["robust_aggregate"] = self._robust.metrics(self.total_workers)
         if int(getattr(self.cfg, "warmup_steps", 0) or 0) > 0:
             m["warmup_steps"] = int(self.cfg.warmup_steps)
             m["effective_lr"] = float(self.lr)

@@ -15,7 +15,8 @@ and adds the MI355X-native knobs: --gpus/--nproc, --codec {non
 --optimizer {sgd,lars,adamw,lamb,muon} with --lars-trust/--lars-eps, --adam-beta1/--adam-beta2/--adam-eps and
 --muon-ns-steps/--muon-aux-lr,
 --warmup-steps (linear lr warmup of the server update),
---dc-lambda/--dc-adaptive (async delay compensation), --clip-norm/--skip-nonfinite (global-norm clipping, non-finite guard), --model,
+--dc-lambda/--dc-adaptive (async delay compensation), --clip-norm/--skip-nonfinite (global-norm clipping, non-finite guard),
+--aggregate {mean,trimmed,median,krum} with --trim/--byzantine (Byzantine-robust combine of a sync round's wires), --model,
 --synthetic, --ckpt-every/--resume, --sync-semantics {barrier,reference}, --topology.
 Precedence: explicit CLI flag > JSON config file (--config) > environment > default.
 """
@@ -115,6 +116,15 @@ class PSConfig:
     # whole-arena updates only: no bucketed overlap, graph round, sharded server, native async loop.
     clip_norm: float = 0.0
     skip_nonfinite: bool = False
+    # how the W gathered wires of a sync round become one gradient (parallel/robust.py,
+    # csrc/kernels/robust.hip): mean (the fp32 sum times 1/W) | trimmed (coordinate-wise, without the
+    # `trim` smallest and largest values; W > 2 trim) | median (coordinate-wise) | krum (multi-Krum: the
+    # mean of the W - byzantine workers closest to their neighbours; W >= 2 byzantine + 3). Every
+    # --optimizer runs behind it. Sync mode, dense wires, the Python server on gathered sources: no
+    # payload codec, native loops, graph round, bucketed overlap, sharded server or --dc-lambda.
+    aggregate: str = "mean"
+    trim: int = 1
+    byzantine: int = 1
     sync_semantics: str = "barrier"  # barrier (wait-for-N) | reference (count-triggered)
     # The reference server never updates BN running statistics and every fetch overwrites the
     # workers' copies (server.py:96,131-133 + worker.py:252), so evaluation runs on near-initial
@@ -217,6 +227,27 @@ class PSConfig:
                                  f"{self.optimizer}")
             if self.dc_lambda > 0.0:
                 raise ValueError("--clip-norm / --skip-nonfinite run on the SGD server update: not with --dc-lambda")
+        if self.aggregate not in ("mean", "trimmed", "median", "krum"):
+            raise ValueError(f"--aggregate must be mean, trimmed, median or krum, got {self.aggregate!r}")
+        if self.aggregate != "mean":
+            agg = f"--aggregate {self.aggregate}"
+            if int(self.trim) < 1 or int(self.byzantine) < 1:
+                raise ValueError(f"{agg}: --trim and --byzantine must be >= 1")
+            if not self.dense_wire:
+                raise ValueError(f"{agg} ranks the workers' dense wires against each other: --codec fp16 or none only, "
+                                 f"not the payload codec {self.codec}")
+            if self.dc_lambda > 0.0:
+                raise ValueError(f"{agg} combines the wires of a sync round: not with --dc-lambda")
+            if self.mode != "sync":
+                raise ValueError(f"{agg} combines the wires of a round, and an async push is one gradient: --mode sync "
+                                 f"only")
+            if self.topology == "sharded":
+                raise ValueError(f"{agg} runs on the rank-0 server's gathered wires: not with --topology sharded")
+            if self.overlap is True:
+                raise ValueError(f"{agg} runs on whole gathered wires: not with --overlap")
+            if os.environ.get("PSX_SYNC_AGG", "gather") != "gather":
+                raise ValueError(f"{agg} needs every worker's wire on the server: PSX_SYNC_AGG="
+                                 f"{os.environ['PSX_SYNC_AGG']} reduces them on the way, unset it (gather)")
         if self.whole_arena_update:
             # a shard boundary or a gradient bucket may split a tensor (lars, lamb, muon); no shard sees the
             # whole gradient, and a bucket is applied before the others have arrived (the guard)
@@ -284,11 +315,12 @@ class PSConfig:
         error-feedback codecs (q8, sign1, topk, powersgd) encode the whole gradient at once, and a whole-arena update
         (whole_arena_update) cannot start before the last bucket: no bucketed rounds. --optimizer
         adamw is element-wise and stays eligible. --fetch-codec q8delta encodes the final arena of a
-        round, which a bucketed round broadcasts piecewise before it exists: no bucketed rounds."""
+        round, which a bucketed round broadcasts piecewise before it exists: no bucketed rounds.
+        --aggregate trimmed / median / krum combines whole gathered wires: no bucketed rounds."""
         if self.overlap is None:
             self.overlap = (world > 1 and self.mode == "sync" and max(1, self.sync_steps) == 1
                             and self.dense_wire and self.topology != "sharded" and not self.whole_arena_update
-                            and self.fetch_codec != "q8delta")
+                            and self.fetch_codec != "q8delta" and self.aggregate == "mean")
         return bool(self.overlap)
 
     @property
@@ -373,6 +405,13 @@ def add_arguments(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
            "clipped); 0 = off (default); implies --skip-nonfinite")
     A("--skip-nonfinite", action="store_true", default=None,
       help="skip a server update whose gradient sum holds inf / NaN (the round still counts)")
+    A("--aggregate", choices=["mean", "trimmed", "median", "krum"], default=None,
+      help="how a sync round's W wires become one gradient: mean (default), trimmed (coordinate-wise mean without "
+           "the --trim smallest and largest values), median (coordinate-wise) or krum (multi-Krum: the mean of the "
+           "W - --byzantine workers closest to their neighbours); sync mode, --codec fp16 / none, Python server")
+    A("--trim", type=int, default=None, help="--aggregate trimmed: values dropped at each end (default 1; W > 2T)")
+    A("--byzantine", type=int, default=None,
+      help="--aggregate krum: bad workers tolerated (default 1; W >= 2F + 3)")
     A("--sync-semantics", choices=["barrier", "reference"], default=None)
     A("--bn-sync", action="store_true", default=None, help="workers push BN running stats; server averages")
     A("--deterministic", dest="deterministic", action="store_true", default=None,
