@@ -27,7 +27,8 @@ struct HeadBnStats {
 // act: NHWC [B][HW][C] of storage type T (bf16 bits or fp32); fcw: [K][C] fp32; fcb: [K] fp32;
 // labels int32 [B]. outputs: pooled [B][C] fp32, dlogits [B][K] fp32 (already divided by B),
 // dact (T, same shape as act; nullable for eval), loss [B] fp32, correct (atomic int counter,
-// nullable). One workgroup per sample; C must be a multiple of 512 or <= 512 and even, K <= 256.
+// nullable). One workgroup per sample; C a multiple of 16 and, past 512, of 512; K <= 1024
+// (head_fused_ok below; the class-row loop takes up to 16 trips of 64 rows).
 template <typename T, bool BWD>
 __global__ __launch_bounds__(256) void head_kernel(const T* __restrict__ act, int HW, int C,
                                                    const float* __restrict__ fcw, const float* __restrict__ fcb, int K,
