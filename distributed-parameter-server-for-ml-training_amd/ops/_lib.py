@@ -155,6 +155,9 @@ _KERNEL_SIGS = {
     "psx_robust_gram": (i32, [vp, i32, i32, i64, vp, vp]),
     "psx_robust_krum_select": (i32, [vp, i32, i32, i32, vp, vp, vp]),
     "psx_robust_select_sum": (i32, [vp, i32, i32, vp, vp, i64, i32, f32, vp]),
+    "psx_robust_iter_state_bytes": (i32, []),
+    "psx_robust_iter_step": (i32, [vp, i32, i32, i64, i32, vp, vp, vp, vp, f32, vp]),
+    "psx_robust_iter_weights": (i32, [vp, i32, i32, i32, f64, f64, i32, vp, vp]),
 }
 
 _RUNTIME_SIGS = {

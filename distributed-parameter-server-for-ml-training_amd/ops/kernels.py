@@ -1317,6 +1317,73 @@ def robust_select_sum(srcs, state: KrumState, agg, m, c=1.0):
                                           float(c), stream_ptr()), "robust_select_sum")
 
 
+ROBUST_ITER_CHUNK = 8192  # kChunk in csrc/kernels/wire.hpp: arena elements per workgroup of the step kernel
+ROBUST_ITER_KINDS = {"init": 0, "mid": 1, "last": 2}
+ROBUST_ITER_RULES = {"geomed": 0, "cclip": 1}
+# IterState in csrc/kernels/robust_iter.hip
+_ROBUST_ITER_STATE = [("a", "<f4", 32), ("b", "<f4"), ("pad", "<f4"), ("d", "<f8", 32), ("rounds", "<i8"),
+                      ("degenerate_rounds", "<i8"), ("clipped", "<i8", 32), ("wsum", "<f8", 32)]
+
+
+class RobustIterState:
+    """The scratch and the device state block of --aggregate geomed / cclip for an arena of ``n``
+    elements: the step kernel's partials [ceil(n / ROBUST_ITER_CHUNK)][32] (double; columns >= W
+    stay zero), the state block (weights a[32] and b, the distances, the counters) and, with
+    ``centre``, the fp32 centre [n] that cclip carries from round to round (zeros at first)."""
+
+    def __init__(self, n, device, centre=False):
+        import numpy as np
+
+        self.n = int(n)
+        assert self.n > 0, "RobustIterState n"
+        self._dtype = np.dtype(_ROBUST_ITER_STATE)
+        assert kernels().psx_robust_iter_state_bytes() == self._dtype.itemsize, "IterState layout"
+        self.nblocks = -(-self.n // ROBUST_ITER_CHUNK)
+        self.partials = torch.zeros(self.nblocks, 32, dtype=torch.float64, device=device)
+        self.state = torch.zeros(self._dtype.itemsize, dtype=torch.uint8, device=device)
+        self.centre = torch.zeros(self.n, dtype=torch.float32, device=device) if centre else None
+        self.device = self.state.device
+
+    def set_weights(self, a, b=0.0):
+        """The weights of the next step, given by hand (a: up to 32 values, the rest zero)."""
+        w = torch.zeros(33, dtype=torch.float32)
+        w[:len(a)] = torch.as_tensor(a, dtype=torch.float32)
+        w[32] = float(b)
+        self.state[:132].copy_(w.view(torch.uint8))
+
+    def read(self) -> dict:
+        """The state block read back (synchronises: for metrics and tests, not per round)."""
+        r = self.state.cpu().numpy().view(self._dtype)[0]
+        return {k: (r[k].tolist() if self._dtype[k].shape else r[k].item()) for k in self._dtype.names if k != "pad"}
+
+
+def robust_iter_step(srcs, state: RobustIterState, kind, agg=None, c=1.0, weights=None):
+    """One pass of csrc/kernels/robust_iter.hip over the W gathered wires (all fp16 or all fp32, >=
+    state.n elements, at most 32) with the weights in the state block, or ``weights`` = (a, b) put
+    there first. ``kind`` "init": state.partials = the squared distances to the centre (zero without
+    one); "mid": centre <- b centre + sum_k a_k g_k, in place when the state has one, and the
+    distances to it; "last": the same centre and agg = c * it. One launch on the current stream."""
+    if weights is not None:
+        state.set_weights(*weights)
+    if kind == "last":
+        _robust_agg(agg, state.n, state.device, "robust_iter_step")
+    taken = tuple(t for t in (agg if kind == "last" else None, state.centre, state.partials) if t is not None)
+    arr, fp16 = _wire_srcs(srcs, state.n, state.device, taken, "robust_iter_step")
+    check(kernels().psx_robust_iter_step(arr, len(srcs), int(fp16), state.n, ROBUST_ITER_KINDS[kind],
+                                         ptr(state.centre), ptr(state.state), ptr(state.partials),
+                                         ptr(agg) if kind == "last" else None, float(c), stream_ptr()),
+          "robust_iter_step")
+
+
+def robust_iter_weights(state: RobustIterState, nsrc, rule, tau=0.0, eps=1e-6, final=False):
+    """The state block's a[32], b and distances from state.partials by the rule's definition
+    ("geomed" with eps = nu, "cclip" with tau); ``final``: the last weights step of a round, which
+    bumps the block's counters. One workgroup, no host synchronisation."""
+    check(kernels().psx_robust_iter_weights(ptr(state.partials), state.nblocks, int(nsrc), ROBUST_ITER_RULES[rule],
+                                            float(tau), float(eps), int(final), ptr(state.state), stream_ptr()),
+          "robust_iter_weights")
+
+
 def grad_aggregate(srcs_dev_ptrs, nsrc, src_fp16, dst, n, scale=1.0, accumulate=False):
     """srcs_dev_ptrs: int64 device tensor holding nsrc device pointers."""
     check(kernels().psx_grad_aggregate(ptr(srcs_dev_ptrs), nsrc, int(src_fp16), ptr(dst),

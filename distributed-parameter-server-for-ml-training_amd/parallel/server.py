@@ -73,7 +73,7 @@ class ParameterServer:
         # --optimizer muon: the Newton-Schulz tile maps and workspaces (ops/kernels.py MuonTable)
         self._muon_tab = K.MuonTable(layout, self.device, self._lars_tab) if self.rule.matrix and self._lars_tab else None
         self._lars_ratios = self._lamb_ratios = self._muon_norms = None
-        # --aggregate trimmed / median / krum (parallel/robust.py): the combine update_range puts in
+        # --aggregate trimmed / median / krum / geomed / cclip (parallel/robust.py): the combine update_range puts in
         # front of the rule; _robust_wires: the wires of an open in-process round
         self._robust = RB.Robust(cfg, self.n, self.device) if getattr(cfg, "aggregate", "mean") != "mean" else None
         self._robust_wires = []
@@ -191,7 +191,7 @@ class ParameterServer:
         and every host form, leaves stale). Several ranges of one round share the momentum 'first
         step' flag and the Adam update number: finish_round_apply closes the round.
 
-        --aggregate trimmed / median / krum (parallel/robust.py): two or more unsummed dense wires are
+        --aggregate trimmed / median / krum / geomed / cclip (parallel/robust.py): two or more unsummed dense wires are
         first combined into the aggregation buffer, agg = e * c with e the robust estimate and c =
         fl(1 / fl(weight)), and the rule goes on with ``[agg], summed=True`` and the same weight. So
         weight * agg is e wherever the core's weight is 1 / W; any other weight (reference

@@ -16,7 +16,8 @@ and adds the MI355X-native knobs: --gpus/--nproc, --codec {non
 --muon-ns-steps/--muon-aux-lr,
 --warmup-steps (linear lr warmup of the server update),
 --dc-lambda/--dc-adaptive (async delay compensation), --clip-norm/--skip-nonfinite (global-norm clipping, non-finite guard),
---aggregate {mean,trimmed,median,krum} with --trim/--byzantine (Byzantine-robust combine of a sync round's wires), --model,
+--aggregate {mean,trimmed,median,krum,geomed,cclip} with --trim/--byzantine/--robust-iters/--cclip-tau/--geomed-eps
+(Byzantine-robust combine of a sync round's wires), --model,
 --synthetic, --ckpt-every/--resume, --sync-semantics {barrier,reference}, --topology.
 Precedence: explicit CLI flag > JSON config file (--config) > environment > default.
 """
@@ -122,9 +123,16 @@ class PSConfig:
     # mean of the W - byzantine workers closest to their neighbours; W >= 2 byzantine + 3). Every
     # --optimizer runs behind it. Sync mode, dense wires, the Python server on gathered sources: no
     # payload codec, native loops, graph round, bucketed overlap, sharded server or --dc-lambda.
+    # geomed (the geometric median of the wires by robust_iters smoothed Weiszfeld steps, floor geomed_eps on a
+    # distance) | cclip (centred clipping: robust_iters steps from the previous round's centre, each wire's
+    # pull clipped to the radius cclip_tau > 0, in units of the gradient norm); both W >= 3, whole gradient
+    # (csrc/kernels/robust_iter.hip).
     aggregate: str = "mean"
     trim: int = 1
     byzantine: int = 1
+    robust_iters: int = 3
+    cclip_tau: float = 0.0
+    geomed_eps: float = 1e-6
     sync_semantics: str = "barrier"  # barrier (wait-for-N) | reference (count-triggered)
     # The reference server never updates BN running statistics and every fetch overwrites the
     # workers' copies (server.py:96,131-133 + worker.py:252), so evaluation runs on near-initial
@@ -227,12 +235,21 @@ class PSConfig:
                                  f"{self.optimizer}")
             if self.dc_lambda > 0.0:
                 raise ValueError("--clip-norm / --skip-nonfinite run on the SGD server update: not with --dc-lambda")
-        if self.aggregate not in ("mean", "trimmed", "median", "krum"):
-            raise ValueError(f"--aggregate must be mean, trimmed, median or krum, got {self.aggregate!r}")
+        if self.aggregate not in ("mean", "trimmed", "median", "krum", "geomed", "cclip"):
+            raise ValueError(f"--aggregate must be mean, trimmed, median, krum, geomed or cclip, got "
+                             f"{self.aggregate!r}")
         if self.aggregate != "mean":
             agg = f"--aggregate {self.aggregate}"
             if int(self.trim) < 1 or int(self.byzantine) < 1:
                 raise ValueError(f"{agg}: --trim and --byzantine must be >= 1")
+            if int(self.robust_iters) < 1:
+                raise ValueError(f"{agg}: --robust-iters must be >= 1")
+            if not self.geomed_eps > 0.0:
+                raise ValueError(f"{agg}: --geomed-eps must be > 0")
+            if self.aggregate == "cclip" and not self.cclip_tau > 0.0:
+                raise ValueError("--aggregate cclip needs its clipping radius: give --cclip-tau > 0. It is in units "
+                                 "of the gradient norm, which only the job knows: a run with --clip-norm reports the "
+                                 "norms it saw (norm_mean in the metrics of the gradient guard), a starting point")
             if not self.dense_wire:
                 raise ValueError(f"{agg} ranks the workers' dense wires against each other: --codec fp16 or none only, "
                                  f"not the payload codec {self.codec}")
@@ -316,7 +333,7 @@ class PSConfig:
         (whole_arena_update) cannot start before the last bucket: no bucketed rounds. --optimizer
         adamw is element-wise and stays eligible. --fetch-codec q8delta encodes the final arena of a
         round, which a bucketed round broadcasts piecewise before it exists: no bucketed rounds.
-        --aggregate trimmed / median / krum combines whole gathered wires: no bucketed rounds."""
+        --aggregate trimmed / median / krum / geomed / cclip combines whole gathered wires: no bucketed rounds."""
         if self.overlap is None:
             self.overlap = (world > 1 and self.mode == "sync" and max(1, self.sync_steps) == 1
                             and self.dense_wire and self.topology != "sharded" and not self.whole_arena_update
@@ -405,10 +422,18 @@ def add_arguments(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
            "clipped); 0 = off (default); implies --skip-nonfinite")
     A("--skip-nonfinite", action="store_true", default=None,
       help="skip a server update whose gradient sum holds inf / NaN (the round still counts)")
-    A("--aggregate", choices=["mean", "trimmed", "median", "krum"], default=None,
+    A("--aggregate", choices=["mean", "trimmed", "median", "krum", "geomed", "cclip"], default=None,
       help="how a sync round's W wires become one gradient: mean (default), trimmed (coordinate-wise mean without "
-           "the --trim smallest and largest values), median (coordinate-wise) or krum (multi-Krum: the mean of the "
-           "W - --byzantine workers closest to their neighbours); sync mode, --codec fp16 / none, Python server")
+           "the --trim smallest and largest values), median (coordinate-wise), krum (multi-Krum: the mean of the "
+           "W - --byzantine workers closest to their neighbours), geomed (the geometric median, --robust-iters "
+           "smoothed Weiszfeld steps) or cclip (centred clipping with the radius --cclip-tau around the previous "
+           "round's centre); sync mode, --codec fp16 / none, Python server")
+    A("--robust-iters", type=int, default=None,
+      help="--aggregate geomed / cclip: steps per round (default 3; each is one more pass over the wires)")
+    A("--cclip-tau", type=float, default=None,
+      help="--aggregate cclip: the clipping radius, in units of the gradient norm (required, > 0)")
+    A("--geomed-eps", type=float, default=None,
+      help="--aggregate geomed: the floor on a wire's distance in its weight 1 / distance (default 1e-6)")
     A("--trim", type=int, default=None, help="--aggregate trimmed: values dropped at each end (default 1; W > 2T)")
     A("--byzantine", type=int, default=None,
       help="--aggregate krum: bad workers tolerated (default 1; W >= 2F + 3)")
